@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """Benchmark of the PermutoSDF data-parallel hot path on MI355X (contract: see the round instructions).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extra]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up and K timed steps and prints the headline line.  --full adds everything else the
+benchmark measures or checks: the CPU baseline, the 24-bit-operand run of the same step, the 24-level, cfg-2 ball, cfg 3 / 4 / 5
+rows and, under N > 1, the device / checksum certificate.  --dump-outputs DIR writes what the last timed step computed
+(dump_outputs below) for output-for-output comparisons of two builds; that step starts from the seeded starting state
+(measure() below), so its outputs are the same in every run up to float rounding.
 
 Workload (BASELINE.json configs[1] + the compositing of configs[2]'s chunk size): per GPU 16 384 rays x 128 samples
 = 2 097 152 synthetic ray samples inside the radius-0.5 bounding sphere, already resident in HBM.  One step =
@@ -121,6 +127,40 @@ def cpu_baseline(cores):
                       % (rays, per_ray, N, reps, dt_s, cores, os.cpu_count() or 0)}
 
 
+DUMP_SAMPLE_ROWS = 2 ** 18       # per-sample arrays beyond the ones written whole: a fixed sample of this many rows
+DUMP_LATTICE_SAMPLE = 2 ** 20    # entries of the updated lattice table
+
+
+def dump_outputs(dirname, hp, pred, saved, loss, res):
+    """Write what the last timed step handed its caller as float32 DIR/<name>.npy, ~48 MB in all: the per-ray radiance, the
+    loss, every sample's SDF, the lattice gradient and the MLP gradients whole; the per-sample radiance and SDF gradients on a
+    fixed sample of rows; the parameters after the AdamW update (the MLP whole, the lattice table on a fixed sample).  The
+    step ran from the seeded starting state (measure()), and the samples are drawn from a constant seed, so two runs with
+    the same arguments write the same entries computed from the same inputs."""
+    os.makedirs(dirname, exist_ok=True)
+    N = saved["sdf"].numel()
+    rng = np.random.default_rng(12345)
+    rows = torch.from_numpy(np.sort(rng.choice(N, min(N, DUMP_SAMPLE_ROWS), replace=False))).to(pred.device)
+    lat = hp.enc.lattice_values.detach().reshape(-1)
+    lat_idx = torch.from_numpy(np.sort(rng.choice(lat.numel(), min(lat.numel(), DUMP_LATTICE_SAMPLE), replace=False))).to(pred.device)
+    grads = res["grads"]
+    arrays = {"radiance": pred, "loss": loss.reshape(-1), "sdf": saved["sdf"].reshape(-1), "grad_lattice": grads[0],
+              "grad_sdf_sample": res["g_sdf"].reshape(-1)[rows], "lattice_after_update_sample": lat[lat_idx]}
+    if res.get("g_rgb") is not None:
+        arrays["grad_rgb_sample"] = res["g_rgb"].reshape(N, -1)[rows]
+    for l, layer in enumerate(hp.mlp.layers):
+        arrays["grad_mlp_weight%d" % l] = grads[1 + 2 * l]
+        arrays["grad_mlp_bias%d" % l] = grads[2 + 2 * l]
+        arrays["mlp_weight%d_after_update" % l] = layer.weight
+        arrays["mlp_bias%d_after_update" % l] = layer.bias
+    host = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= 64 * 2 ** 20, "dump of %d bytes exceeds 64 MB" % total
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return total
+
+
 def main():
     if len(sys.argv) >= 3 and sys.argv[1] == "--cpu-baseline-child":
         print(json.dumps(cpu_baseline(int(sys.argv[2]))), flush=True)
@@ -130,9 +170,17 @@ def main():
     # defaults: 200 steps of ~3 ms keep the GPU busy for ~0.6 s, long enough for an outside sampler (rocm-smi) to see the load
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra 24-level row (profiling runs: one kernel variant per name)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else (CPU baseline, 24-bit operands, other "
+                         "sizes and configurations, the N > 1 certificate); a plain run prints the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the extra rows (profiling runs: one kernel variant per name)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB), e.g. bench_outputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from permuto_sdf_amd import parallel
     from permuto_sdf_amd.hotpath import SdfHotPath
@@ -165,31 +213,60 @@ def main():
     _lp.restype = ctypes.c_int
     K = args.steps
 
+    def restore(h, params0):
+        """back to the seeded starting state in place: the parameters as constructed, zero AdamW moments and step counts"""
+        with torch.no_grad():
+            for p, p0 in zip(h.params, params0):
+                p.copy_(p0)
+                st = h.opt.state.get(p)
+                if st:
+                    st["exp_avg"].zero_()
+                    st["exp_avg_sq"].zero_()
+                    st["step"] = 0
+
     def measure(h, warmup):
-        """W untimed warm-up steps, then EXACTLY K timed steps between two barriers; per-kernel-family HIP events on the launch
+        """W untimed warm-up steps, then EXACTLY K timed steps between barriers; per-kernel-family HIP events on the launch
         stream (torch's current stream == the stream the kernels are launched on).  -> (elapsed seconds of this rank, events,
-        (mlp backward path, mlp forward path) the timed steps dispatched to)"""
+        (mlp backward path, mlp forward path) the timed steps dispatched to, (pred, saved, loss, backward result) of the last
+        timed step).  The steps train: the encode backward sums with float atomics, so from the second step on the state
+        differs between runs at rounding level, and AdamW and the L1 loss's sign gradient let that grow.  The last timed step
+        therefore starts from the seeded starting state again (restored between barriers, outside the timed span): it
+        computes the same thing from the same inputs in every run."""
+        params0 = [p.detach().clone() for p in h.params]
         for _ in range(warmup):
             h.step(rs, rgb, normals, gt)
         ev_ = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
                for k in ("enc_bwd", "mlp_bwd", "fwd", "mlp_fwd", "comm_wait")}
+        el = 0.0
         barrier()
         t0_ = time.perf_counter()
         for i in range(K):
+            if i + 1 == K:
+                barrier()
+                el += time.perf_counter() - t0_
+                restore(h, params0)
+                barrier()
+                t0_ = time.perf_counter()
             h.events = {"enc_bwd": ev_["enc_bwd"][i], "mlp_bwd": ev_["mlp_bwd"][i], "comm_wait": ev_["comm_wait"][i],
                         "mlp_fwd": ev_["mlp_fwd"][i]}
             ev_["fwd"][i][0].record()
             pred, saved = h.forward(rs, rgb, normals)
             ev_["fwd"][i][1].record()
             loss, g_pred = l1_loss_raw(pred, gt)
-            h.backward(rs, rgb, saved, g_pred)
+            if i + 1 < K:
+                h.backward(rs, rgb, saved, g_pred)
+            else:               # the last step's results are kept for --dump-outputs
+                last_ = (pred, saved, loss, h.backward(rs, rgb, saved, g_pred))
         barrier()
-        el = time.perf_counter() - t0_
+        el += time.perf_counter() - t0_
         h.events = None
         # which kernels the timed steps dispatched to (debug query of the library; read NOW, later launches change it)
-        return el, ev_, (int(_lp(ctypes.c_int(1))), int(_lp(ctypes.c_int(2))))
+        return el, ev_, (int(_lp(ctypes.c_int(1))), int(_lp(ctypes.c_int(2)))), last_
 
-    elapsed, ev, (path_bwd, path_fwd) = measure(hp, args.warmup)
+    elapsed, ev, (path_bwd, path_fwd), last = measure(hp, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hp, *last)
+    del last
     extra = {}
     cdev = dev if (world == 1 or torch.distributed.get_backend() == "nccl") else "cpu"
     t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -208,7 +285,7 @@ def main():
     # (uuid / PCI bus id: N distinct ones, or the run says otherwise), the collective library's version, and whether the
     # replicas still hold bit-identical parameters after the timed steps (a checksum per rank, MIN == MAX over ranks)
     cert = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             pr = torch.cuda.get_device_properties(dev)
             ident = "%s|%s|%s" % (getattr(pr, "uuid", "?"), getattr(pr, "pci_bus_id", "?"), getattr(pr, "name", "?"))
@@ -389,7 +466,7 @@ def main():
                          "note": "buckets: MLP gradients first (overlap the encode backward), then the lattice gradient in two level "
                                  "ranges (the first range travels while the second is computed); comm_wait_ms = what the step still "
                                  "waits for after its last backward kernel"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # The vectorised torch-CPU restatement gets SLOWER beyond ~8 threads on the 256-core host (measured:
             # 8 thr 0.7 s, 32 thr 1.1 s, 64 thr 2.2 s per 32k samples), so the baseline uses 8 threads and says so.
             # It runs in a child process under a hard timeout: the baseline must never take the GPU number down.
@@ -402,6 +479,14 @@ def main():
             except Exception as e:
                 out["cpu_baseline"] = {"value": None, "unit": "samples/s", "cores": cores, "kind": "port",
                                        "sample": "failed: %r" % (e,)}
+    if not args.full:
+        # a plain run ends here: everything below measures or checks something besides the headline
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if torch.distributed.is_initialized():
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
     # ---- everything below is EXTRA: the headline (`out`, rank 0) is complete.  A watchdog prints it and ends the process if the
     # extras -- which under N > 1 contain collectives -- do not come back: they must never cost the driver its line.
     import threading
@@ -453,7 +538,7 @@ def main():
             os.environ["PSDF_MLP_FWD_SPLIT"] = "bf16"
             os.environ["PSDF_MLP_BWD_SPLIT"] = "bf16"
             hpb = SdfHotPath(nr_levels=NR_LEVELS, hidden=64, out_channels=1, device=dev, seed=0)
-            el_b, ev_b, (pb_bwd, pb_fwd) = measure(hpb, max(3, min(args.warmup, 10)))
+            el_b, ev_b, (pb_bwd, pb_fwd), _ = measure(hpb, max(3, min(args.warmup, 10)))
             tb_ = torch.tensor([el_b], dtype=torch.float64, device=cdev)
             if world > 1:
                 torch.distributed.all_reduce(tb_, op=torch.distributed.ReduceOp.MAX)

@@ -31,7 +31,7 @@ def build(ref=True, quiet=True):
     out = subprocess.DEVNULL if quiet else None
     subprocess.run(["make", "-C", HERE, "oracle"], check=True, stdout=out)
     if ref and os.path.isdir("/root/reference/kernels"):
-        subprocess.run(["make", "-C", HERE, "ref"], check=True, stdout=out)
+        subprocess.run(["make", "-C", HERE, "ref", "ref_fma"], check=True, stdout=out)
     return os.path.exists(PORT_LIB), os.path.exists(REF_LIB)
 
 

@@ -30,14 +30,14 @@ def test_two_rank_training_keeps_replicas_identical(manual):
 
 
 def test_two_rank_bench_line_certifies_itself():
-    """bench.py under N = 2 (both ranks on cuda:0, gloo): the line carries dp.certificate -- one device identity per rank, the
+    """bench.py --full under N = 2 (both ranks on cuda:0, gloo): the line carries dp.certificate -- one device identity per rank, the
     collective backend, and MIN == MAX over ranks of a parameter checksum after the timed steps (replicas bit-identical).  On
     real hardware the same block says `distinct_devices == n_gpus` and names the RCCL version."""
     env = dict(os.environ)
     env.update(PSDF_BENCH_SINGLE_DEVICE="1", PSDF_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extra"]
+           "--full", "--no-cpu-baseline", "--no-extra"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

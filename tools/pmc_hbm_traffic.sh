@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/pmc_hbm_$TAG
 mkdir -p $OUT
 cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra > $OUT/$C.log 2>&1
+  timeout 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -- python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra > $OUT/$C.log 2>&1
 done
 cd $R
 python - "$OUT" "$TAG" <<'PY'
@@ -55,7 +55,7 @@ for n in names_all:
         res[n]["class"] = "gather (line fills of L2-resident tables: FETCH_SIZE as reported)" if n in gather else "streaming (FETCH_SIZE x 2)"
         res[n]["hbm_bytes"] = int(k * res[n]["fetch_kib"] * 1024 + res[n]["write_kib"] * 1024)
 doc = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python bench.py --steps 3 "
-                 "--warmup 1 --no-cpu-baseline --no-extra (since round 6 that command times the step twice: two fp16 pieces per MLP "
+                 "--warmup 1 --full --no-cpu-baseline --no-extra (since round 6 that command times the step twice: two fp16 pieces per MLP "
                  "operand -- mlp_*_split_f16 / mlp_fwd_split_kernel[f16] -- and three bf16 pieces -- mlp_bwd_split_kernel, "
                  "mlp_fwd_split_kernel[bf16]); MI355X; units KiB per launch (mean over launches)",
        "correction": "gfx950: FETCH_SIZE reports 1/2 of the bytes of wide coalesced reads (MI355X_MICROARCH.md, HBM section; "

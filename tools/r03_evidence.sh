@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03
 mkdir -p $O
 cd $R
-python bench.py --steps 50 --warmup 5 > $O/bench_final.json 2> $O/bench_final.err
+python bench.py --steps 50 --warmup 5 --full > $O/bench_final.json 2> $O/bench_final.err
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_bench -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 cd $R

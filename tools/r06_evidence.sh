@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r06
 mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 PSDF_BENCH_NO_24BIT=1 bash tools/kstats.sh $O/bench_kernel_stats.txt -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra
 PSDF_BENCH_NO_24BIT=1 PSDF_MLP_FWD_SPLIT=bf16 PSDF_MLP_BWD_SPLIT=bf16 bash tools/kstats.sh $O/bench_24bit_kernel_stats.txt -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra
 bash tools/kstats.sh $O/cfg4_manual_kernel_stats.txt -- python $R/tools/train_bench.py --manual --start-iter 20000 --repeats 1
