@@ -169,8 +169,11 @@ unsigned psdf_mlp_f16_range_events(void);
    Forward of the reference's colour network shape (LipshitzMLP 111 -> 128 -> 128 -> 64 -> 3, models.py:54-129,349-350: dims[0] <= 112,
    dims[1], dims[2] <= 128, dims[3] <= 64, dims[4] <= 16) on the fp16 matrix pipe with two pieces per fp32 operand: X [dims[0], N],
    Y [dims[4], N] feature-major; weights[l] [dims[l+1], dims[l]] (for a LipshitzMLP the NORMALISED weights), biases[l]; GELU between
-   the layers, the last one linear.  -2: another shape, stream capture, PSDF_MLP_WIDE_SPLIT=f32, or a value beyond the fp16 range met
-   earlier (psdf_mlp_forward evaluates every shape with fp32 MFMAs). */
+   the layers, the last one linear.  N == 0: PSDF_OK before any pointer is looked at, nothing touched.  -2: another shape, stream
+   capture, PSDF_MLP_WIDE_SPLIT=f32, or a value beyond the fp16 range met by an earlier launch (psdf_mlp_forward evaluates every shape
+   with fp32 MFMAs).  Range guard: an input, hidden activation or weight of magnitude >= 32768 raises this launch's guard word; the
+   same launch then redoes the batch with fp32 MFMAs on the device (Y is exact to the fp32 kernel's bar, never inf / NaN from the
+   split), and raises the process-wide switch that makes later calls return -2. */
 int psdf_mlp_forward_wide_f16(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
     const float* const* biases, float* Y, void* stream);
 /* which kernel the last psdf_mlp_backward_wide launched: 1 = fp32 MFMAs (mlp_wide_bwd_kernel), 2 = two fp16 pieces per operand on
@@ -183,7 +186,12 @@ int psdf_mlp_backward_wide_form(void);
    share a 32-sample tile through LDS, each owns one output tile per layer.  -2 for other widths / no stream-ordered scratch;
    psdf_mlp_backward falls through to it.  Also (split-fp16 kernel only): the 64-wide nets with many outputs (background density
    net 52 -> 64 x 3 -> 65, models.py:451-459) and, with n_layers = 3, the background colour head 80 -> 64 -> 64 -> 3
-   (models.py:463-469: 64 < dims[0] <= 80, 32 < dims[1], dims[2] <= 64, dims[3] <= 16). */
+   (models.py:463-469: 64 < dims[0] <= 80, 32 < dims[1], dims[2] <= 64, dims[3] <= 4: the heads the single-wave fp32 redo covers).  N == 0: PSDF_OK before any pointer is
+   looked at, nothing touched.  Range guard of the split-fp16 kernel: |input| >= 32, |hidden activation| >= 128 (the H side of the
+   parameter-gradient products is pre-scaled by 2^10 / 2^8), |dZ of the per-sample scaled chain| >= 32768 or |weight| >= 32768
+   raise the launch's own guard word: its gradient images are dropped and the fp32 kernel (4 layers: mlp_wide_bwd_kernel; 3: the
+   single-wave head kernel) queued behind it -- a no-op otherwise -- redoes the batch in the same call; the process-wide switch goes
+   up with it, and later calls take the fp32 kernel outright (psdf_mlp_backward_wide_form() == 1). */
 int psdf_mlp_backward_wide(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
     const float* const* biases, const float* dY, float* dX, float* const* dW, float* const* db, void* stream);
 

@@ -164,6 +164,10 @@ struct BwdPtrs {
   float* db[MAXL];
   float* partial;  // [gridDim.x][p.total] workgroup gradient images (summed by mlp_grad_reduce_kernel), or NULL: atomics
   const unsigned char* skip = nullptr;  // [N] or NULL: 16-sample tiles whose samples are all masked are not evaluated
+  // NULL, or a device word that must hold only_if_token for the launches to do anything (the redo of a batch the split-fp16 head
+  // kernel of mlp_wide.hip declined, queued behind it); with it, `partial` is the caller's scratch and is used as given
+  const uint32_t* only_if = nullptr;
+  uint32_t only_if_token = 0u;
 };
 
 // Workgroup gradient image -> global.  With a scratch buffer every workgroup stores its image (coalesced, no atomics:
@@ -195,6 +199,7 @@ __device__ __forceinline__ void flush_image(const Plan16& p, const BwdPtrs& a, c
 constexpr int GRW = 16;
 __global__ void __launch_bounds__(GRW * 64) mlp_grad_reduce_kernel(Plan16 p, BwdPtrs a, int nimages) {
   __shared__ float part[GRW][64];
+  if (a.only_if && a.only_if[0] != a.only_if_token) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int e = blockIdx.x * 64 + lane;
   float s = 0.f;
@@ -469,6 +474,7 @@ __global__ void __launch_bounds__(NW * 64)
     mlp_bwd_kernel(Plan16 p, int64_t N, const float* __restrict__ X, const float* __restrict__ dY,
                    float* __restrict__ dX, BwdPtrs a) {
   extern __shared__ __align__(16) float lds[];
+  if (a.only_if && a.only_if[0] != a.only_if_token) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   constexpr int SX = 4 * TI0;                       // k-steps of layer 0 (upper bound of p.steps0)
   constexpr int WAVE_LDS = 16 * 17 + 16 + 2 * SX * 64;
@@ -836,6 +842,7 @@ __global__ void __launch_bounds__(BW * 64)
   static_assert(T3 > 0, "three hidden layers");
   static_assert(!(Y2 && FINAL_DOT), "the fused plain backward exists for nets with a matrix output layer");
   extern __shared__ __align__(16) float lds[];
+  if (a.only_if && a.only_if[0] != a.only_if_token) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   constexpr int SX = 4 * TI0;
   constexpr int WAVE_LDS = 16 * 17 + 16 + 4 * SX * 64;   // transpose buffer, dy, 2 x X tile, 2 x V tile
@@ -1193,7 +1200,7 @@ int launch_dbl_bwd(const Plan16& p, int64_t N, const float* X, const float* V, c
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
   if (e != hipSuccess) return (int)e;
   BwdPtrs ap = a;
-  ap.partial = grad_scratch_alloc((size_t)blocks * p.total, st);
+  if (!a.only_if) ap.partial = grad_scratch_alloc((size_t)blocks * p.total, st);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BW * 64), shmem, st, p, N, X, V, dY, dY2, dX2, ap);
   grad_scratch_reduce(p, ap, (int)blocks, st);
   PSDF_LAUNCH_CHECK();
@@ -1242,7 +1249,7 @@ int launch_bwd_nw(const Plan16& p, int64_t N, const float* X, const float* dY, f
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), shmem, st, p, N, X, dY, dX, ap);                 \
   } while (0)
   BwdPtrs ap = a;
-  ap.partial = grad_scratch_alloc((size_t)blocks * p.total, st);
+  if (!a.only_if) ap.partial = grad_scratch_alloc((size_t)blocks * p.total, st);
   if (dX)
     GO(true);
   else
@@ -1266,6 +1273,39 @@ int launch_bwd(const Plan16& p, int64_t N, const float* X, const float* dY, floa
 }
 
 }  // namespace
+
+namespace psdf {
+// The background colour head 80 -> 64 x 2 -> 3 on the fp32-MFMA kernel, every launch conditional on *only_if == token (redo the
+// batch), gradient images in `scratch` (mlp_backward_head_redo_bytes(N) bytes): the range-guard redo behind the split-fp16 head
+// kernel of mlp_wide.hip.  dW, db ACCUMULATED into, dX overwritten (when given).
+size_t mlp_backward_head_redo_bytes(int64_t N) {
+  const int dims[4] = {80, 64, 64, 3};
+  Plan16 p;
+  if (make_plan16(3, dims, p) != PSDF_OK) return 0;
+  int64_t blocks = ((N + 15) / 16 + BW - 1) / BW;
+  if (blocks > 256) blocks = 256;
+  return ((size_t)blocks * p.total * sizeof(float) + 255) & ~(size_t)255;
+}
+int mlp_backward_head_redo(const int* dims, int64_t N, const float* X, const float* const* weights, const float* const* biases,
+                           const float* dY, float* dX, float* const* dW, float* const* db, hipStream_t st, char* scratch,
+                           const uint32_t* only_if, uint32_t token) {
+  Plan16 p;
+  int rc = make_plan16(3, dims, p);
+  if (rc != PSDF_OK) return rc;
+  if (p.tiles[0] != 5 || p.tiles[1] != 4 || p.tiles[2] != 4 || p.tiles[3] != 1 || !p.final_dot) return PSDF_ERR_UNSUPPORTED;
+  BwdPtrs a;
+  for (int l = 0; l < MAXL; l++) {
+    a.W[l] = l < 3 ? weights[l] : nullptr;
+    a.b[l] = l < 3 ? biases[l] : nullptr;
+    a.dW[l] = l < 3 ? dW[l] : nullptr;
+    a.db[l] = l < 3 ? db[l] : nullptr;
+  }
+  a.partial = reinterpret_cast<float*>(scratch);
+  a.only_if = only_if;
+  a.only_if_token = token;
+  return launch_bwd_nw<5, 4, 4, 0, 1, true, true, BW>(p, N, X, dY, dX, a, st);
+}
+}  // namespace psdf
 
 #ifdef PSDF_BWD_TIMING
 extern "C" int psdf_debug_bwd_timing(unsigned long long* out) {

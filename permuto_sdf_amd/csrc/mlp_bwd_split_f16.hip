@@ -358,12 +358,17 @@ __device__ __forceinline__ void layer_bwd(const f32x4 (&dz)[NT], f32x4 (&dh)[NTO
 }
 
 // Range guard.  The two-piece scheme holds while every input and hidden activation stays below 2^8 in magnitude (the H-side
-// dW operand is pre-scaled by 2^8 and fp16 ends at 65504) and every weight below 65504.  The kernels keep the largest |x|, |h|
+// dW operand is pre-scaled by 2^8 and fp16 ends at 65504), every weight below 65504 and the last layer's below W4_LIMIT.  The kernels keep the largest |x|, |h|
 // they meet (one v_max3_f32 per two values, 32 per tile) and raise the launch's guard word (absmax[1]) when it reaches
 // RANGE_LIMIT; the pack kernel does the same for the weights.  A raised word makes the summing launch drop the images and lets
 // the three-piece bf16 kernel -- queued behind every launch, a no-op while the word is zero -- redo the batch (dX is
 // overwritten): psdf_mlp_backward_split_f16 below.
 constexpr float RANGE_LIMIT = 255.0f;
+// The chain's dZ is split into two fp16 pieces as well.  dZ3 = w4 dY' gelu'(z3) with |dY'| < 2^5 (the per-sample scaling) and
+// gelu' < 1.13, so |w4| < W4_LIMIT keeps it below 32768 -- checked on the weights by the pack kernel, nothing per tile (a running
+// maximum of dZ inside the kernel moved the baseline instantiation's register allocation: 184 -> 205 AGPRs).  dZ2, dZ1 are not
+// guarded.
+constexpr float W4_LIMIT = 32768.0f / (32.0f * 1.13f);
 __device__ __forceinline__ float amax_of(float m, const f32x4& v) {
   m = __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fabsf(v[0])), __builtin_fabsf(v[1]));
   return __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fabsf(v[2])), __builtin_fabsf(v[3]));
@@ -822,7 +827,10 @@ __global__ void mlp_split_pack_kernel(int K0, const float* __restrict__ W0, cons
     if (e < HID) tail[e] = b0[e];
     else if (e < 2 * HID) tail[e] = b1[e - HID];
     else if (e < 3 * HID) tail[e] = b2[e - 2 * HID];
-    else if (e < 4 * HID) tail[e] = W3[e - 3 * HID];
+    else if (e < 4 * HID) {
+      tail[e] = W3[e - 3 * HID];
+      if (__builtin_fabsf(W3[e - 3 * HID]) >= W4_LIMIT) atomicOr(absmax + 1, 1u);     // range guard of dZ3 (see W4_LIMIT)
+    }
     else if (e == 4 * HID) tail[e] = b3[0];
   }
 }

@@ -19,6 +19,9 @@
 #include "psdf_common.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <atomic>
+#include <mutex>
+#include <vector>
 
 namespace {
 
@@ -148,11 +151,14 @@ struct GImg {
 // T4 = output tiles of the (linear) last layer: 1 for the colour network (3 outputs), 5 for the background density / feature
 // net 52 -> 64 x 3 -> 65 (models.py:451-459), whose single-wave fp32 kernel ran out of the register file (213-227 spilled
 // registers, 209 us per call at 23 k samples: the second most expensive kernel of the training step until round 3).
+// only_if: NULL, or a device word that must hold `token` for the launch to do anything (the range-guard redo behind a split-fp16
+// launch, see wide_launch_f16)
 template <int TI0, int T1, int T2, int T3, int T4>
 __global__ void __launch_bounds__(WN * 64, 1)
     mlp_wide_bwd_kernel(WideArgs a, int64_t N, const float* __restrict__ X, const float* __restrict__ dY,
-                        float* __restrict__ dX, float* __restrict__ partial) {
+                        float* __restrict__ dX, float* __restrict__ partial, const uint32_t* __restrict__ only_if, uint32_t token) {
   static_assert(TI0 <= WN && T1 <= WN && T2 <= WN && T3 <= WN && T4 <= WN, "one output tile per wave and layer");
+  if (only_if && only_if[0] != token) return;
   extern __shared__ __align__(16) float lds[];
   float* H0 = lds;                         // [TI0*16][RS]   inputs
   float* H1 = H0 + TI0 * 16 * RS;          // activations
@@ -276,11 +282,15 @@ __global__ void __launch_bounds__(WN * 64, 1)
   if (wave < T4) { put(GI::W4, T3 * 16, wave, T3, dW4); put_db(GI::B4, wave, db4); }
 }
 
-// sum of the workgroup images -> ACCUMULATED into the torch-layout gradients of the (normalised) weights
+// sum of the workgroup images -> ACCUMULATED into the torch-layout gradients of the (normalised) weights.  only_if (NULL or a word
+// that must hold `token`, as above); drop_if (NULL or the range-guard word of the split-fp16 launch whose images these are: holding
+// `token`, the guard was raised by that launch, the images are dropped and the fp32 launches queued behind redo the batch)
 template <int TI0, int T1, int T2, int T3, int T4>
 __global__ void mlp_wide_reduce_kernel(const float* __restrict__ partial, int nimg, WideArgs a, float* dW0, float* dW1,
-                                       float* dW2, float* dW3, float* db0, float* db1, float* db2, float* db3) {
+                                       float* dW2, float* dW3, float* db0, float* db1, float* db2, float* db3,
+                                       const uint32_t* __restrict__ only_if, const uint32_t* __restrict__ drop_if, uint32_t token) {
   using GI = GImg<TI0, T1, T2, T3, T4>;
+  if ((only_if && only_if[0] != token) || (drop_if && drop_if[0] == token)) return;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= GI::TOTAL) return;
   float s = 0.f;
@@ -305,9 +315,12 @@ struct PackLayers {
   int out[4], in[4], out_pad[4], in_pad[4];
   const float* W[4];
   float* Wp[4];
-  float* WTp[4];
+  float* WTp[4];      // NULL: no transposed copy (the forward)
+  const uint32_t* only_if;
+  uint32_t token;
 };
 __global__ void mlp_wide_pack_kernel(PackLayers p) {
+  if (p.only_if && p.only_if[0] != p.token) return;
   const int l = blockIdx.y;
   const int out = p.out[l], in = p.in[l], out_pad = p.out_pad[l], in_pad = p.in_pad[l];
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -315,7 +328,7 @@ __global__ void mlp_wide_pack_kernel(PackLayers p) {
   const int o = e / in_pad, i = e % in_pad;
   const float v = (o < out && i < in) ? p.W[l][o * in + i] : 0.f;
   p.Wp[l][e] = v;
-  p.WTp[l][i * out_pad + o] = v;
+  if (p.WTp[l]) p.WTp[l][i * out_pad + o] = v;
 }
 
 // Lipschitz weight normalisation of one layer (models.py:98-104): Wn[r][:] = W[r][:] * min(1, softplus(c) / sum_j |W[r][j]|).
@@ -409,17 +422,28 @@ __global__ void __launch_bounds__(64) lipshitz_norm_multi_kernel(LipLayers p, in
   }
 }
 
-// pack (both weight orientations, zero padded), main launch, summing launch
+// bytes of scratch wide_launch needs
 template <int TI0, int T1, int T2, int T3, int T4>
-int wide_launch(const int* dims, int64_t N, const float* X, const float* const* weights, const float* const* biases,
-                const float* dY, float* dX, float* const* dW, float* const* db, hipStream_t st) {
-  using GI = GImg<TI0, T1, T2, T3, T4>;
+size_t wide_launch_bytes(int64_t N) {
   const int pads[5] = {TI0 * 16, T1 * 16, T2 * 16, T3 * 16, T4 * 16};
   size_t wfloats = 0;
   for (int l = 0; l < 4; l++) wfloats += 2 * (size_t)pads[l] * pads[l + 1];
   const int64_t ntiles = (N + TS - 1) / TS;
+  const int64_t blocks = ntiles < 256 ? ntiles : 256;
+  return (wfloats + (size_t)blocks * GImg<TI0, T1, T2, T3, T4>::TOTAL) * sizeof(float);
+}
+
+// pack (both weight orientations, zero padded), main launch, summing launch.  scratch_in: NULL (the stream's scratch), or
+// wide_launch_bytes(N) bytes of the caller's; only_if: see mlp_wide_bwd_kernel
+template <int TI0, int T1, int T2, int T3, int T4>
+int wide_launch(const int* dims, int64_t N, const float* X, const float* const* weights, const float* const* biases,
+                const float* dY, float* dX, float* const* dW, float* const* db, hipStream_t st, char* scratch_in = nullptr,
+                const uint32_t* only_if = nullptr, uint32_t token = 0u) {
+  using GI = GImg<TI0, T1, T2, T3, T4>;
+  const int pads[5] = {TI0 * 16, T1 * 16, T2 * 16, T3 * 16, T4 * 16};
+  const int64_t ntiles = (N + TS - 1) / TS;
   int64_t blocks = ntiles < 256 ? ntiles : 256;
-  char* scratch = (char*)psdf::stream_scratch((wfloats + (size_t)blocks * GI::TOTAL) * sizeof(float), st);  // NULL while capturing
+  char* scratch = scratch_in ? scratch_in : (char*)psdf::stream_scratch(wide_launch_bytes<TI0, T1, T2, T3, T4>(N), st);  // NULL while capturing
   if (!scratch) return PSDF_ERR_UNSUPPORTED;
   WideArgs a;
   PackLayers pk;
@@ -437,18 +461,102 @@ int wide_launch(const int* dims, int64_t N, const float* X, const float* const* 
     a.WT[l] = WTp;
     a.b[l] = biases[l];
   }
+  pk.only_if = only_if;
+  pk.token = token;
   hipLaunchKernelGGL(mlp_wide_pack_kernel, dim3((nmax + 255) / 256, 4), dim3(256), 0, st, pk);
   for (int i = 0; i < 5; i++) a.dims[i] = dims[i];
   float* partial = wp;
   const size_t lds_bytes = (size_t)((TI0 + 2 * T1 + 2 * T2 + 2 * T3 + T4) * 16) * RS * sizeof(float);
   auto kern = mlp_wide_bwd_kernel<TI0, T1, T2, T3, T4>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  static hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);   // once
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WN * 64), lds_bytes, st, a, N, X, dY, dX, partial);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WN * 64), lds_bytes, st, a, N, X, dY, dX, partial, only_if, token);
   // (the small nets' images: 32 slices of the workgroup images instead of 8 -- their summing launch waits on loads, not on bytes)
   hipLaunchKernelGGL((mlp_wide_reduce_kernel<TI0, T1, T2, T3, T4>), dim3((GI::TOTAL + 255) / 256, GI::TOTAL < 20000 ? 32 : 8), dim3(256), 0, st, partial,
-                     (int)blocks, a, dW[0], dW[1], dW[2], dW[3], db[0], db[1], db[2], db[3]);
+                     (int)blocks, a, dW[0], dW[1], dW[2], dW[3], db[0], db[1], db[2], db[3], only_if, (const uint32_t*)nullptr, token);
   PSDF_LAUNCH_CHECK();
+  return PSDF_OK;
+}
+
+// Forward on the fp32 MFMAs (the layers of the backward's recompute, the last one linear): the range-guard redo behind the
+// split-fp16 forward (wide_forward_f16), conditional on *only_if == token.  Y [dims[4], N] feature-major, overwritten.
+template <int TI0, int T1, int T2, int T3, int T4>
+__global__ void __launch_bounds__(WN * 64, 1)
+    mlp_wide_fwd_kernel(WideArgs a, int64_t N, const float* __restrict__ X, float* __restrict__ Y, const uint32_t* __restrict__ only_if,
+                        uint32_t token) {
+  if (only_if && only_if[0] != token) return;
+  extern __shared__ __align__(16) float lds[];
+  float* H0 = lds;
+  float* H1 = H0 + TI0 * 16 * RS;
+  float* H2 = H1 + T1 * 16 * RS;
+  float* H3 = H2 + T2 * 16 * RS;
+  float* H4 = H3 + T3 * 16 * RS;           // [T4*16][RS]: the linear layer's output
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+  const int K0 = a.dims[0], OUT = a.dims[4];
+  const int64_t ntiles = (N + TS - 1) / TS;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t n0 = tile * TS;
+    __syncthreads();
+    for (int e = threadIdx.x; e < TI0 * 16 * TS; e += WN * 64) {
+      const int row = e / TS, s = e % TS;
+      const int64_t n = n0 + s;
+      H0[row * RS + s] = (row < K0 && n < N) ? X[(int64_t)row * N + n] : 0.f;
+    }
+    __syncthreads();
+    if (wave < T1) layer_fwd<TI0, true>(a.W[0], TI0 * 16, a.b[0], a.dims[1], wave, H0, H1, nullptr, c, g);
+    __syncthreads();
+    if (wave < T2) layer_fwd<T1, true>(a.W[1], T1 * 16, a.b[1], a.dims[2], wave, H1, H2, nullptr, c, g);
+    __syncthreads();
+    if (wave < T3) layer_fwd<T2, true>(a.W[2], T2 * 16, a.b[2], a.dims[3], wave, H2, H3, nullptr, c, g);
+    __syncthreads();
+    if (wave < T4) layer_fwd<T3, false>(a.W[3], T3 * 16, a.b[3], OUT, wave, H3, H4, nullptr, c, g);
+    __syncthreads();
+    for (int e = threadIdx.x; e < OUT * TS; e += WN * 64) {
+      const int row = e / TS, s = e % TS;
+      const int64_t n = n0 + s;
+      if (n < N) Y[(int64_t)row * N + n] = H4[row * RS + s];
+    }
+  }
+}
+
+template <int TI0, int T1, int T2, int T3, int T4>
+size_t wide_forward_bytes() {
+  const int pads[5] = {TI0 * 16, T1 * 16, T2 * 16, T3 * 16, T4 * 16};
+  size_t wfloats = 0;
+  for (int l = 0; l < 4; l++) wfloats += (size_t)pads[l] * pads[l + 1];
+  return wfloats * sizeof(float);
+}
+// zero-padded weights (forward orientation only) into `scratch` (wide_forward_bytes), forward launch; both conditional on
+// *only_if == token
+template <int TI0, int T1, int T2, int T3, int T4>
+int wide_forward(const int* dims, int64_t N, const float* X, const float* const* weights, const float* const* biases, float* Y,
+                 hipStream_t st, char* scratch, const uint32_t* only_if, uint32_t token) {
+  const int pads[5] = {TI0 * 16, T1 * 16, T2 * 16, T3 * 16, T4 * 16};
+  WideArgs a;
+  PackLayers pk;
+  float* wp = reinterpret_cast<float*>(scratch);
+  int nmax = 0;
+  for (int l = 0; l < 4; l++) {
+    const int n = pads[l] * pads[l + 1];
+    pk.out[l] = dims[l + 1], pk.in[l] = dims[l], pk.out_pad[l] = pads[l + 1], pk.in_pad[l] = pads[l];
+    pk.W[l] = weights[l], pk.Wp[l] = wp, pk.WTp[l] = nullptr;
+    a.W[l] = wp;
+    a.WT[l] = nullptr;
+    a.b[l] = biases[l];
+    wp += n;
+    nmax = n > nmax ? n : nmax;
+  }
+  pk.only_if = only_if;
+  pk.token = token;
+  hipLaunchKernelGGL(mlp_wide_pack_kernel, dim3((nmax + 255) / 256, 4), dim3(256), 0, st, pk);
+  for (int i = 0; i < 5; i++) a.dims[i] = dims[i];
+  const int64_t ntiles = (N + TS - 1) / TS;
+  const int64_t blocks = ntiles < 512 ? ntiles : 512;
+  const size_t lds_bytes = (size_t)((TI0 + T1 + T2 + T3 + T4) * 16) * RS * sizeof(float);
+  auto kern = mlp_wide_fwd_kernel<TI0, T1, T2, T3, T4>;
+  static hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);   // once
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WN * 64), lds_bytes, st, a, N, X, Y, only_if, token);
   return PSDF_OK;
 }
 
@@ -537,9 +645,30 @@ struct WideArgsH {
   const wu32x4* AT[4];   // transposed: [in tile][k-step over the outputs][piece][lane]
   const float* b[4];
   int dims[5];
-  uint32_t* overflow;    // host-mapped word: some |value| left the fp16 range (the launcher then falls back to the fp32 kernel)
+  uint32_t* guard;       // range guard of the stream (wide_guard_word): set to `token`, the number of THIS launch, when raised; the
+  uint32_t token;        // fp32 launches queued behind compare it with the same number and redo the batch
+  uint32_t* sticky;      // host-mapped word, raised with it: later calls take the fp32 kernels outright
 };
 constexpr int wns(int tiles) { return (tiles + 1) / 2; }   // k-steps (32 features) covering `tiles` 16-feature tiles
+
+// Range guard.  Every value that is split into two fp16 pieces must stay below 65504 (the high piece, rounded to nearest, is
+// inf from 65520 on).  The kernels keep the largest of them -- inputs and hidden activations as they enter the T records (times the
+// pre-scale below), the chain's dZ, the weights in the pack kernel -- and raise both guard words at WIDE_LIMIT (half the range).
+// The H side of the parameter-gradient products is pre-scaled by an exact power of two (taken out again with the tile's fold):
+// the encoding's lattice features start at 1e-5, an fp16 subnormal, whose low piece would be empty (3e-3 .. 2e-1 relative error
+// of a dW1 column instead of ~1e-6; tests/test_gpu_mlp_wide_numerics.py).  Limits: inputs below 32, hidden activations below 128,
+// dZ and weights below 32768.
+constexpr float WIDE_LIMIT = 32768.f;
+constexpr int PRE_X = 10;      // inputs (the T records of dW1's H side)
+constexpr int PRE_H = 8;       // hidden activations (dW2 .. dW4)
+__device__ __forceinline__ void wide_report(float m, uint32_t* guard, uint32_t token, uint32_t* sticky) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0 && m >= WIDE_LIMIT) {
+    if (guard) atomicExch(guard, token);
+    if (sticky) atomicOr(sticky, 1u);
+  }
+}
 
 // weight records of all four layers, both orientations: blockIdx.y = layer * 2 + orientation, thread = (tile, k-step, lane)
 struct PackH {
@@ -547,6 +676,9 @@ struct PackH {
   const float* W[4];
   wu32x4* A[4];
   wu32x4* AT[4];
+  uint32_t* guard;      // as in WideArgsH
+  uint32_t token;
+  uint32_t* sticky;
 };
 __global__ void mlp_wide_f16_pack_kernel(PackH p) {
   const int l = blockIdx.y >> 1, tr = blockIdx.y & 1;
@@ -565,12 +697,18 @@ __global__ void mlp_wide_f16_pack_kernel(PackH p) {
     w[j] = (o < p.out[l] && i < p.in[l]) ? p.W[l][o * p.in[l] + i] : 0.f;
   }
   wu32x4 hi, lo;
+  float wmax = 0.f;
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     uint32_t h, l2;
     wsplit2(w[2 * q], w[2 * q + 1], h, l2);
     hi[q] = h;
     lo[q] = l2;
+    wmax = fmaxf(wmax, fmaxf(fabsf(w[2 * q]), fabsf(w[2 * q + 1])));
+  }
+  if (wmax >= WIDE_LIMIT) {
+    if (p.guard) atomicExch(p.guard, p.token);
+    if (p.sticky) atomicOr(p.sticky, 1u);
   }
   wu32x4* dst = (tr ? p.AT[l] : p.A[l]) + ((size_t)(t * ks + s) * 2) * 64 + lane;
   dst[0] = hi;
@@ -779,7 +917,10 @@ __global__ void __launch_bounds__(WN * 64, 1)
     float hs[2];             // 2^(kmin - k(n)) <= 1: the H side of the parameter-gradient products
 #pragma unroll
     for (int sb = 0; sb < 2; sb++) hs[sb] = (kmin - kk[sb] < -120) ? 0.f : __uint_as_float((uint32_t)(127 + kmin - kk[sb]) << 23);
-    const float fold = __uint_as_float((uint32_t)(127 - kmin) << 23);   // 2^-kmin
+    // 2^-kmin, and the pre-scales of the H side taken out with it
+    const float fold_x = __uint_as_float((uint32_t)(127 - kmin - PRE_X) << 23), fold_h = __uint_as_float((uint32_t)(127 - kmin - PRE_H) << 23);
+    const float hs_x[2] = {hs[0] * (float)(1 << PRE_X), hs[1] * (float)(1 << PRE_X)};
+    const float hs_h[2] = {hs[0] * (float)(1 << PRE_H), hs[1] * (float)(1 << PRE_H)};
     // ---- stage the inputs (wave = (k-step, sample block)): B records, and the same values scaled and transposed as T records
     if (wave < NS0 * 2) {
       const int s = wave >> 1, sb = wave & 1;
@@ -787,7 +928,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         x[j] = px[j];
-        vmax = fmaxf(vmax, fabsf(x[j]));
+        vmax = fmaxf(vmax, fabsf(x[j]) * (float)(1 << PRE_X));
       }
       wu32x4 hi, lo;
 #pragma unroll
@@ -800,7 +941,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
       wu32x4* rec = B0 + (s * 2 + sb) * 128 + lane;
       rec[0] = hi;
       rec[64] = lo;
-      const float f = hs[sb];
+      const float f = hs_x[sb];
       put_t1(X0T + (2 * s) * 128, sb, f32x4{x[0] * f, x[1] * f, x[2] * f, x[3] * f});
       if (2 * s + 1 < TI0) put_t1(X0T + (2 * s + 1) * 128, sb, f32x4{x[4] * f, x[5] * f, x[6] * f, x[7] * f});
     }
@@ -880,8 +1021,10 @@ __global__ void __launch_bounds__(WN * 64, 1)
         wgelu4(acc[sb], h[sb], gp[sb]);
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-          hsc[sb][r] = h[sb][r] * hs[sb];
-          vmax = fmaxf(vmax, fabsf(h[sb][r]));
+          hsc[sb][r] = h[sb][r] * hs_h[sb];
+          // (the bound of the T record AND of the unscaled B record: hs_h / 2^PRE_H <= 1 can be 2^-96 for a sample without
+          //  upstream gradient, and its |h| still goes into the chain's B records as it is)
+          vmax = fmaxf(vmax, fabsf(h[sb][r]) * (float)(1 << PRE_H));
         }
       }
       put_b(Bout, wave, h);
@@ -890,7 +1033,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
     };
     // dW rows of the own tile: dZ^T (own scratch) x H^T (T records), folded into the running sums
     // (the scratch was written before the last barrier, by the wave that owns the tile in the chain)
-    auto dw = [&](const wu32x4* Sset, const wu32x4* Tin, int tout, int tin, int cn, f32x4* run) {
+    auto dw = [&](const wu32x4* Sset, const wu32x4* Tin, int tout, int tin, int cn, f32x4* run, float fold) {
       const int sl = wave / tout, to = wave - sl * tout;       // slice of the columns, row tile
       const WRec za = wload(Sset + to * 128 + lane);
       for (int i = 0; i < cn; i++) {
@@ -910,6 +1053,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
         for (int r = 0; r < 4; r++) {
           acc[sb][r] *= gp[sb][r];
           db[r] = fmaf(acc[sb][r], dn[sb], db[r]);
+          vmax = fmaxf(vmax, fabsf(acc[sb][r]));
         }
       put_b(Bout, wave, acc);
       put_t(Sset + wave * 128, acc);
@@ -960,7 +1104,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
       WDBG
     }
     // ---- backward.  The linear last layer: its upstream gradient is in B4 / set A of the scratch
-    if (wave < S4 * T4) dw(SA, L3 ? H3T : H2T, T4, TL, C4, dW4);
+    if (wave < S4 * T4) dw(SA, L3 ? H3T : H2T, T4, TL, C4, dW4, fold_h);
     if constexpr (L3) {
       if (wave < T3) {
         acc[0] = zero2[0], acc[1] = zero2[1];
@@ -971,7 +1115,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
       WDBG
       __syncthreads();
       WDBG
-      if (wave < S3 * T3) dw(SB, H2T, T3, T2, C3, dW3);
+      if (wave < S3 * T3) dw(SB, H2T, T3, T2, C3, dW3, fold_h);
     }
     if (wave < T2) {
       acc[0] = zero2[0], acc[1] = zero2[1];
@@ -982,7 +1126,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
     WDBG
     __syncthreads();
     WDBG
-    if (wave < S2 * T2) dw(S2set, H1T, T2, T1, C2, dW2);
+    if (wave < S2 * T2) dw(S2set, H1T, T2, T1, C2, dW2, fold_h);
     if (wave < T1) {
       acc[0] = zero2[0], acc[1] = zero2[1];
       mma(NS2, B2, acc);
@@ -992,7 +1136,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
     WDBG
     __syncthreads();
     WDBG
-    if (wave < S1 * T1) dw(S1set, X0T, T1, TI0, C1, dW1);
+    if (wave < S1 * T1) dw(S1set, X0T, T1, TI0, C1, dW1, fold_x);
     if (dX && wave < TI0) {
       acc[0] = zero2[0], acc[1] = zero2[1];
       mma(NS1, B1, acc);
@@ -1006,7 +1150,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
         }
     }
   }
-  if (vmax >= 32768.f && a.overflow) atomicOr(a.overflow, 1u);
+  wide_report(vmax, a.guard, a.token, a.sticky);
   // ---- the wave's accumulators -> this workgroup's gradient image (the layout of the fp32 kernel)
   using GI = GImg<TI0, T1, T2, T3, T4>;
   float* img = partial + (size_t)blockIdx.x * GI::TOTAL;
@@ -1171,7 +1315,7 @@ __global__ void __launch_bounds__(WN * 64, 2)
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (vmax >= 32768.f && a.overflow) atomicOr(a.overflow, 1u);
+  wide_report(vmax, a.guard, a.token, a.sticky);
 }
 
 static uint32_t* wide_overflow_word() {
@@ -1187,9 +1331,52 @@ static uint32_t* wide_overflow_word() {
   return w;
 }
 int g_wide_form = 0;    // 1 = fp32 MFMA kernel, 2 = split-fp16 kernel (last launch)
+}  // namespace
+namespace psdf {
+size_t mlp_backward_head_redo_bytes(int64_t N);      // mlp_bwd.hip
+int mlp_backward_head_redo(const int* dims, int64_t N, const float* X, const float* const* weights, const float* const* biases,
+                           const float* dY, float* dX, float* const* dW, float* const* db, hipStream_t st, char* scratch,
+                           const uint32_t* only_if, uint32_t token);
+}  // namespace psdf
+namespace {
+constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// The range-guard word of a stream: a launch that meets a value beyond its range stores its own number (wide_guard_token) there, and
+// the launches queued behind it compare the word with that number -- no clearing launch in front of every call, and a launch on
+// another stream has another word.  Allocated (zero) once per stream and device; NULL when that fails (the caller then declines).
+static uint32_t* wide_guard_word(hipStream_t st) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  struct Entry {
+    hipStream_t st;
+    int dev;
+    uint32_t* w;
+  };
+  static std::mutex mu;
+  static std::vector<Entry> entries;
+  std::lock_guard<std::mutex> lock(mu);
+  for (auto& x : entries)
+    if (x.st == st && x.dev == dev) return x.w;
+  uint32_t* w = nullptr;
+  if (hipMalloc((void**)&w, 256) != hipSuccess || hipMemset(w, 0, 256) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  entries.push_back(Entry{st, dev, w});
+  return w;
+}
+static uint32_t wide_guard_token() {
+  static std::atomic<uint32_t> n{0};
+  uint32_t t = ++n;
+  while (t == 0u) t = ++n;        // (0: the word's initial value)
+  return t;
+}
 
 // n_layers = 4: dims {in, h1, h2, h3, out}; n_layers = 3 (T3 == 0): dims {in, h1, h2, out} -- the linear last layer then sits in slot 3
-// of the kernel's arrays and slot 2 stays empty
+// of the kernel's arrays and slot 2 stays empty.  Range guard: a launch that meets a value beyond its limit stores its own number
+// (wide_guard_token) in the stream's guard word (wide_guard_word; never cleared); the summing launch drops the images when the word
+// holds that number, and the fp32 path queued behind (4 layers: wide_launch; 3: the single-wave head kernel of mlp_bwd.hip) -- a
+// no-op unless the word holds it -- redoes the batch.  A launch on another stream has another word: it cannot make the drop and
+// the redo see different values.
 template <int TI0, int T1, int T2, int T3, int T4>
 int wide_launch_f16(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights, const float* const* biases,
                     const float* dY, float* dX, float* const* dW, float* const* db, hipStream_t st) {
@@ -1202,8 +1389,15 @@ int wide_launch_f16(int n_layers, const int* dims, int64_t N, const float* X, co
   for (int l = 0; l < 4; l++) nrec += (size_t)out_t[l] * wns(in_t[l]) * 128 + (size_t)in_t[l] * wns(out_t[l]) * 128;
   const int64_t ntiles = (N + TS - 1) / TS;
   int64_t blocks = ntiles < 256 ? ntiles : 256;
-  char* scratch = (char*)psdf::stream_scratch(nrec * 16 + (size_t)blocks * GI::TOTAL * sizeof(float), st);  // NULL while capturing
-  if (!scratch) return PSDF_ERR_UNSUPPORTED;
+  const size_t main_bytes = align256(nrec * 16 + (size_t)blocks * GI::TOTAL * sizeof(float));
+  size_t redo_bytes;
+  if constexpr (T3 > 0) redo_bytes = wide_launch_bytes<TI0, T1, T2, T3, T4>(N);
+  else redo_bytes = psdf::mlp_backward_head_redo_bytes(N);
+  char* scratch = (char*)psdf::stream_scratch(main_bytes + redo_bytes, st);  // NULL while capturing
+  uint32_t* guard = scratch ? wide_guard_word(st) : nullptr;
+  if (!guard) return PSDF_ERR_UNSUPPORTED;
+  const uint32_t token = wide_guard_token();
+  char* redo_scratch = scratch + main_bytes;
   WideArgsH a;
   PackH pk;
   wu32x4* wp = reinterpret_cast<wu32x4*>(scratch);
@@ -1225,7 +1419,9 @@ int wide_launch_f16(int n_layers, const int* dims, int64_t N, const float* X, co
     nmax = n2 > nmax ? n2 : nmax;
   }
   for (int i = 0; i < 5; i++) a.dims[i] = kd[i];
-  a.overflow = wide_overflow_word();
+  a.guard = pk.guard = guard;
+  a.token = pk.token = token;
+  a.sticky = pk.sticky = wide_overflow_word();
   hipLaunchKernelGGL(mlp_wide_f16_pack_kernel, dim3((nmax + 255) / 256, 8), dim3(256), 0, st, pk);
   float* partial = reinterpret_cast<float*>(wp);
   const size_t lds_bytes = (size_t)((wns(TI0) + wns(T1) + wns(T2) + wns(T3) + wns(T4)) * 256 + (TI0 + T1 + T2 + T3) * 128 + 2 * WN * 128 + T4 * 128) * 16 + (size_t)T4 * 32 * 4;
@@ -1245,9 +1441,10 @@ int wide_launch_f16(int n_layers, const int* dims, int64_t N, const float* X, co
   }
   // (the small nets' images: 32 slices of the workgroup images instead of 8 -- their summing launch waits on loads, not on bytes)
   hipLaunchKernelGGL((mlp_wide_reduce_kernel<TI0, T1, T2, T3, T4>), dim3((GI::TOTAL + 255) / 256, GI::TOTAL < 20000 ? 32 : 8), dim3(256), 0, st, partial,
-                     (int)blocks, ar, gw[0], gw[1], gw[2], gw[3], gb[0], gb[1], gb[2], gb[3]);
+                     (int)blocks, ar, gw[0], gw[1], gw[2], gw[3], gb[0], gb[1], gb[2], gb[3], (const uint32_t*)nullptr, guard, token);
   PSDF_LAUNCH_CHECK();
-  return PSDF_OK;
+  if constexpr (T3 > 0) return wide_launch<TI0, T1, T2, T3, T4>(dims, N, X, weights, biases, dY, dX, dW, db, st, redo_scratch, guard, token);
+  else return psdf::mlp_backward_head_redo(dims, N, X, weights, biases, dY, dX, dW, db, st, redo_scratch, guard, token);
 }
 
 template <int TI0, int T1, int T2, int T3, int T4>
@@ -1256,8 +1453,11 @@ int wide_forward_f16(const int* dims, int64_t N, const float* X, const float* co
   const int tiles[5] = {TI0, T1, T2, T3, T4};
   size_t nrec = 0;
   for (int l = 0; l < 4; l++) nrec += (size_t)tiles[l + 1] * wns(tiles[l]) * 128;
-  char* scratch = (char*)psdf::stream_scratch(nrec * 16, st);  // NULL while capturing
-  if (!scratch) return PSDF_ERR_UNSUPPORTED;
+  // the weight records, the fp32 redo's padded weights (see wide_launch_f16)
+  char* scratch = (char*)psdf::stream_scratch(align256(nrec * 16) + wide_forward_bytes<TI0, T1, T2, T3, T4>(), st);  // NULL while capturing
+  uint32_t* guard = scratch ? wide_guard_word(st) : nullptr;
+  if (!guard) return PSDF_ERR_UNSUPPORTED;
+  const uint32_t token = wide_guard_token();
   WideArgsH a;
   PackH pk;
   wu32x4* wp = reinterpret_cast<wu32x4*>(scratch);
@@ -1273,7 +1473,9 @@ int wide_forward_f16(const int* dims, int64_t N, const float* X, const float* co
     nmax = n1 > nmax ? n1 : nmax;
   }
   for (int i = 0; i < 5; i++) a.dims[i] = dims[i];
-  a.overflow = wide_overflow_word();
+  a.guard = pk.guard = guard;
+  a.token = pk.token = token;
+  a.sticky = pk.sticky = wide_overflow_word();
   hipLaunchKernelGGL(mlp_wide_f16_pack_kernel, dim3((nmax + 255) / 256, 8), dim3(256), 0, st, pk);
   const int64_t ntiles = (N + TS - 1) / TS;
   int64_t blocks = ntiles < 512 ? ntiles : 512;
@@ -1283,7 +1485,10 @@ int wide_forward_f16(const int* dims, int64_t N, const float* X, const float* co
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WN * 64), lds_bytes, st, a, N, X, Y);
   PSDF_LAUNCH_CHECK();
-  return PSDF_OK;
+  // the redo on the fp32 MFMAs, a no-op unless this launch raised its guard
+  const int rc = wide_forward<TI0, T1, T2, T3, T4>(dims, N, X, weights, biases, Y, st, scratch + align256(nrec * 16), guard, token);
+  PSDF_LAUNCH_CHECK();
+  return rc;
 }
 
 }  // namespace
@@ -1298,7 +1503,8 @@ extern "C" {
 int psdf_mlp_forward_wide_f16(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
                               const float* const* biases, float* Y, void* stream) {
   if (n_layers != 4 || !dims) return PSDF_ERR_UNSUPPORTED;
-  if (N <= 0 || !X || !weights || !biases || !Y) return PSDF_ERR_ARG;
+  if (N == 0) return PSDF_OK;      // before any pointer is looked at (mlp_forward_impl's contract)
+  if (N < 0 || !X || !weights || !biases || !Y) return PSDF_ERR_ARG;
   for (int l = 0; l < 4; l++)
     if (!weights[l] || !biases[l]) return PSDF_ERR_ARG;
   const char* sp = getenv("PSDF_MLP_WIDE_SPLIT");
@@ -1382,8 +1588,10 @@ int psdf_lipshitz_normalize_backward_multi(int n_layers, const int* out, const i
 int psdf_mlp_backward_wide(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
                            const float* const* biases, const float* dY, float* dX, float* const* dW, float* const* db,
                            void* stream) {
-  if ((n_layers != 4 && n_layers != 3) || !dims || !dW || !db) return PSDF_ERR_UNSUPPORTED;
-  if (N <= 0 || !X || !weights || !biases || !dY) return PSDF_ERR_ARG;
+  if ((n_layers != 4 && n_layers != 3) || !dims) return PSDF_ERR_UNSUPPORTED;
+  if (N == 0) return PSDF_OK;      // before any pointer is looked at: nothing to do, nothing touched (psdf_mlp_backward's contract)
+  if (!dW || !db) return PSDF_ERR_UNSUPPORTED;
+  if (N < 0 || !X || !weights || !biases || !dY) return PSDF_ERR_ARG;
   for (int l = 0; l < n_layers; l++)
     if (!weights[l] || !biases[l] || !dW[l] || !db[l]) return PSDF_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
@@ -1391,8 +1599,11 @@ int psdf_mlp_backward_wide(int n_layers, const int* dims, int64_t N, const float
     // two hidden layers: the background colour head 80 -> 64 -> 64 -> 3 (models.py:463-469), split-fp16 kernel only (round 6)
     const char* sp3 = getenv("PSDF_MLP_WIDE_SPLIT");
     uint32_t* ov3 = wide_overflow_word();
-    if ((sp3 && sp3[0] == 'f' && sp3[1] == '3') || (ov3 && *(volatile uint32_t*)ov3)) return PSDF_ERR_UNSUPPORTED;
-    if (dims[0] > 64 && dims[0] <= 80 && dims[1] > 32 && dims[1] <= 64 && dims[2] > 32 && dims[2] <= 64 && dims[3] <= 16) {
+    if ((sp3 && sp3[0] == 'f' && sp3[1] == '3') || (ov3 && *(volatile uint32_t*)ov3)) {
+      g_wide_form = 1;        // (the caller's single-wave fp32 kernel takes the call)
+      return PSDF_ERR_UNSUPPORTED;
+    }
+    if (dims[0] > 64 && dims[0] <= 80 && dims[1] > 32 && dims[1] <= 64 && dims[2] > 32 && dims[2] <= 64 && dims[3] <= 4) {
       g_wide_form = 2;
       return wide_launch_f16<5, 4, 4, 0, 1>(3, dims, N, X, weights, biases, dY, dX, dW, db, st);
     }

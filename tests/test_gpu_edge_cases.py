@@ -51,6 +51,34 @@ def test_empty_batches(dev):
     assert dx_only.shape == (52, 0)
 
 
+@pytest.mark.parametrize("dims", [[111, 128, 128, 64, 3], [52, 64, 64, 64, 65], [36, 64, 64, 64, 33], [80, 64, 64, 3]])
+def test_empty_batches_wide_nets(dev, dims):
+    """N == 0 through the wide split-fp16 kernels (csrc/mlp_wide.hip): the raw C entry points return PSDF_OK with NULL pointers
+    (nothing is looked at), and FusedMLP gives empty outputs and all-zero parameter gradients"""
+    import ctypes
+    from permuto_sdf_amd import FusedMLP
+    from permuto_sdf_amd import _lib as L
+    from permuto_sdf_amd.mlp import _dims_array
+    nl = len(dims) - 1
+    null = ctypes.c_void_p(0)
+    fwd = L.lib().psdf_mlp_forward_wide_f16
+    fwd.restype = ctypes.c_int
+    bwd = L.lib().psdf_mlp_backward_wide
+    bwd.restype = ctypes.c_int
+    if nl == 4:
+        assert fwd(L.c_i(4), _dims_array(dims), L.c_l(0), null, null, null, null, L.stream()) == 0
+    assert bwd(L.c_i(nl), _dims_array(dims), L.c_l(0), null, null, null, null, null, null, null, L.stream()) == 0
+    torch.manual_seed(1)
+    m = FusedMLP(dims).to(dev)
+    x = torch.zeros(0, dims[0], device=dev, requires_grad=True)
+    y = m(x)
+    assert y.shape == (0, dims[-1])
+    y.sum().backward()
+    assert x.grad is not None and x.grad.shape == (0, dims[0])
+    for p in m.parameters():
+        assert p.grad is not None and float(p.grad.abs().sum()) == 0.0
+
+
 def test_single_sample_backward_and_double_backward(dev):
     """N = 1: one partially filled 16-sample tile, seven idle waves per workgroup"""
     from permuto_sdf_amd import FusedMLP

@@ -566,13 +566,14 @@ def test_split_f16_backward_matches_float64(dev, K0, N, dy_scale):
                arr(dWs), arr(dbs), L.stream()) == -2
 
 
-@pytest.mark.parametrize("what", ["inputs", "hidden", "weights"])
+@pytest.mark.parametrize("what", ["inputs", "hidden", "weights", "dz"])
 def test_split_f16_backward_range_guard(dev, what):
     """The two-piece fp16 arithmetic holds for |inputs|, |hidden activations| < 2^8 (the H-side operand of the parameter-gradient
     products is pre-scaled by 2^8) and |weights| < 65504.  Outside, the kernel raises a guard word, its summing launch drops
     the clipped images and the three-piece bf16 kernel queued behind it redoes the batch: the gradients are right (float64,
     the same 2e-5 bar) instead of silently clipped, and the event is counted (psdf_mlp_f16_range_events).  A batch inside the
-    range leaves the counter alone."""
+    range leaves the counter alone.  "dz": the last layer's weights scaled so that the chain's dZ (the kernel runs it on dY[n]
+    scaled into [2^4, 2^5)) passes 65504 while inputs, activations and weights stay inside their limits (asserted in float64)."""
     import copy
     import ctypes
     from permuto_sdf_amd import _lib as L
@@ -587,9 +588,23 @@ def test_split_f16_backward_range_guard(dev, what):
     elif what == "hidden":
         with torch.no_grad():
             lin[0].bias[7] = 400.0                 # h1[:, 7] ~ 400 for every sample
-    else:
+    elif what == "weights":
         with torch.no_grad():
             lin[1].weight[3, 9] = 7.0e4            # a weight fp16 cannot hold
+    else:
+        with torch.no_grad():
+            lin[3].weight.mul_(1.0e5)              # |w4| up to ~1.2e4: dZ3 = w4 dy' gelu'(z3) with |dy'| in [16, 32)
+        Ws = [l.weight.detach().double() for l in lin]
+        H, zs = [x.double().cpu()], []
+        for i, l in enumerate(lin):
+            z = H[-1] @ Ws[i].t() + l.bias.detach().double()
+            zs.append(z)
+            if i < 3:
+                H.append(torch.nn.functional.gelu(z))
+        gp3 = 0.5 * (1 + torch.erf(zs[2] / 2 ** 0.5)) + zs[2] * torch.exp(-0.5 * zs[2] ** 2) / (2 * torch.pi) ** 0.5
+        dz3 = 16.0 * Ws[3].abs() * gp3.abs()                     # a lower bound: every sample's scaled |dY'| is >= 16
+        assert float(dz3.max()) > 65504 and float(x.abs().max()) < 255 and max(float(h.abs().max()) for h in H[1:]) < 255
+        assert max(float(w.abs().max()) for w in Ws) < 65504
     net = torch.nn.Sequential(lin[0], torch.nn.GELU(), lin[1], torch.nn.GELU(), lin[2], torch.nn.GELU(), lin[3]).to(dev)
     gy = torch.randn(N, 1, device=dev)
     events = L.lib().psdf_mlp_f16_range_events
