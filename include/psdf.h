@@ -90,7 +90,7 @@ int psdf_encode_double_backward_ws(int pos_dim, int nr_feat, int64_t N, int nr_l
 
 /* ---- mlp.hip, opt-in arithmetic ---- */
 /* psdf_mlp_pack / psdf_mlp_forward with TWO fp16 pieces per fp32 operand (three products on v_mfma_f32_32x32x16_f16) instead of
-   three bf16 pieces (six products): the BASELINE net only (dims = {<= 64, 64, 64, 64, <= 4}; -2 otherwise); max error ~3e-6 of
+   three bf16 pieces (six products): the BASELINE net only (dims = {<= 64, 64, 64, 64, <= 4}: baseline_split_shape of csrc/mlp_dispatch.h; -2 otherwise); max error ~3e-6 of
    the largest output instead of ~1e-6; inputs, activations and weights must stay below 65504 in magnitude.  A buffer made by
    psdf_mlp_pack_f16 is consumed by psdf_mlp_forward_f16 only. */
 int psdf_mlp_pack_f16(int n_layers, const int* dims, const float* const* weights, const float* const* biases, float* packed,
@@ -137,16 +137,38 @@ int psdf_nerf_composite_backward(int nr_rays, const int* start_end, int equal, i
      family 2 MLP forward    : 1 fp32-MFMA kernel, 2 split-bf16 kernel, 3 split-fp16 kernel (psdf_mlp_forward_f16)
    0 = no call yet, -1 = unknown family. */
 int psdf_last_path(int family);
+/* Which MLP widths have a fused kernel (host only: no device work, no environment read).  op: one of PSDF_MLP_OP_*, naming an
+   entry point: FORWARD psdf_mlp_forward(_masked), FORWARD_F16 psdf_mlp_forward_f16, FORWARD_WIDE_F16 psdf_mlp_forward_wide_f16,
+   BACKWARD psdf_mlp_backward with dW / db, BACKWARD_DATA the same with dW = db = NULL, BACKWARD_DATA_MASKED
+   psdf_mlp_backward_data_masked, DOUBLE_BACKWARD psdf_mlp_double_backward, DOUBLE_BACKWARD_PLUS psdf_mlp_double_backward_plus.
+   1: a kernel is instantiated for these widths and the entry point launches it; 0: the entry point returns -2 for them; -1:
+   argument error (unknown op, dims NULL, n_layers outside 2..5, a width <= 0).  Computed from the dispatch table the entry
+   points expand (csrc/mlp_dispatch.h), LDS limits included.  It reports which kernels exist for the widths, not the runtime
+   demotions: stream capture, PSDF_MLP_BWD_SPLIT / PSDF_MLP_WIDE_SPLIT, the fp16 range guard and the large-batch (N >= 2^18)
+   split backward are not looked at -- so {K0 <= 16, 64, 64, 64, 1}, which only that split backward serves, answers 0. */
+enum {
+  PSDF_MLP_OP_FORWARD = 0,
+  PSDF_MLP_OP_FORWARD_F16 = 1,
+  PSDF_MLP_OP_FORWARD_WIDE_F16 = 2,
+  PSDF_MLP_OP_BACKWARD = 3,
+  PSDF_MLP_OP_BACKWARD_DATA = 4,
+  PSDF_MLP_OP_BACKWARD_DATA_MASKED = 5,
+  PSDF_MLP_OP_DOUBLE_BACKWARD = 6,
+  PSDF_MLP_OP_DOUBLE_BACKWARD_PLUS = 7
+};
+int psdf_mlp_supported(int op, int n_layers, const int* dims);
 
 /* ---- mlp_bwd_split.hip ---- */
-/* same contract as psdf_mlp_backward for dims = {K0 <= 52, 64, 64, 64, 1} with dW/db requested, computed on the bf16 matrix
+/* same contract as psdf_mlp_backward for dims = {K0 <= 52, 64, 64, 64, 1} (baseline_split_shape of csrc/mlp_dispatch.h and
+   the kernel's LDS limit) with dW/db requested, computed on the bf16 matrix
    pipe with split fp32 operands (three bf16 pieces, six products kept: fp32-level accuracy); -2 for every other net and when
    stream-ordered scratch is unavailable (stream capture).  psdf_mlp_backward routes large batches here by itself. */
 int psdf_mlp_backward_split(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
     const float* const* biases, const float* dY, float* dX, float* const* dW, float* const* db, void* stream);
 
 /* ---- mlp_bwd_split_f16.hip ---- */
-/* same contract as psdf_mlp_backward for dims = {K0 <= 64, 64, 64, 64, 1} with dW/db requested, computed on the fp16 matrix pipe
+/* same contract as psdf_mlp_backward for dims = {K0 <= 64, 64, 64, 64, 1} (baseline_split_shape of csrc/mlp_dispatch.h) with
+   dW/db requested, computed on the fp16 matrix pipe
    with TWO fp16 pieces per fp32 operand (three products in the chains, four in the dW products); the gradient chain of every
    sample runs on the mantissa of its dY and the factor 2^e is restored exactly, so the accuracy does not depend on the size or
    spread of dY (errors of a few 1e-6 of the largest entry against float64; activations / weights must stay below 65504 in
@@ -165,9 +187,9 @@ unsigned psdf_mlp_f16_range_events(void);
 
 /* ---- mlp_wide.hip ---- */
 /* (also, round 6: the background density / feature net 52 -> 64 x 3 -> 65, models.py:451-459: dims[0] <= 64, 32 < dims[1..3] <= 64,
-   16 < dims[4] <= 80)
+   16 < dims[4] <= 80 -- density_net_shape of csrc/mlp_dispatch.h)
    Forward of the reference's colour network shape (LipshitzMLP 111 -> 128 -> 128 -> 64 -> 3, models.py:54-129,349-350: dims[0] <= 112,
-   dims[1], dims[2] <= 128, dims[3] <= 64, dims[4] <= 16) on the fp16 matrix pipe with two pieces per fp32 operand: X [dims[0], N],
+   dims[1], dims[2] <= 128, dims[3] <= 64, dims[4] <= 16: colour_net_shape of csrc/mlp_dispatch.h) on the fp16 matrix pipe with two pieces per fp32 operand: X [dims[0], N],
    Y [dims[4], N] feature-major; weights[l] [dims[l+1], dims[l]] (for a LipshitzMLP the NORMALISED weights), biases[l]; GELU between
    the layers, the last one linear.  N == 0: PSDF_OK before any pointer is looked at, nothing touched.  -2: another shape, stream
    capture, PSDF_MLP_WIDE_SPLIT=f32, or a value beyond the fp16 range met by an earlier launch (psdf_mlp_forward evaluates every shape
@@ -181,12 +203,12 @@ int psdf_mlp_forward_wide_f16(int n_layers, const int* dims, int64_t N, const fl
    value beyond the fp16 range met by an earlier launch); 0 = none yet.  Debug query (host only). */
 int psdf_mlp_backward_wide_form(void);
 /* same contract as psdf_mlp_backward for 4-layer nets wider than one wave's register file holds (dims[0] <= 112, dims[1],
-   dims[2] <= 128, dims[3] <= 64, dims[4] <= 16): the colour network LipshitzMLP 111 -> 128 -> 128 -> 64 -> 3 of
+   dims[2] <= 128, dims[3] <= 64, dims[4] <= 16: colour_net_shape of csrc/mlp_dispatch.h): the colour network LipshitzMLP 111 -> 128 -> 128 -> 64 -> 3 of
    permuto_sdf_py/models/models.py:54-129,349-350 (weights = the already normalised ones).  Workgroup-cooperative: 8 waves
    share a 32-sample tile through LDS, each owns one output tile per layer.  -2 for other widths / no stream-ordered scratch;
    psdf_mlp_backward falls through to it.  Also (split-fp16 kernel only): the 64-wide nets with many outputs (background density
-   net 52 -> 64 x 3 -> 65, models.py:451-459) and, with n_layers = 3, the background colour head 80 -> 64 -> 64 -> 3
-   (models.py:463-469: 64 < dims[0] <= 80, 32 < dims[1], dims[2] <= 64, dims[3] <= 4: the heads the single-wave fp32 redo covers).  N == 0: PSDF_OK before any pointer is
+   net 52 -> 64 x 3 -> 65, models.py:451-459: density_net_shape, hidden layers of 33..64) and, with n_layers = 3, the background colour head 80 -> 64 -> 64 -> 3
+   (models.py:463-469: 64 < dims[0] <= 80, 48 < dims[1], dims[2] <= 64, dims[3] <= 4: the heads the single-wave fp32 redo covers; colour_head_shape).  N == 0: PSDF_OK before any pointer is
    looked at, nothing touched.  Range guard of the split-fp16 kernel: |input| >= 32, |hidden activation| >= 128 (the H side of the
    parameter-gradient products is pre-scaled by 2^10 / 2^8), |dZ of the per-sample scaled chain| >= 32768 or |weight| >= 32768
    raise the launch's own guard word: its gradient images are dropped and the fp32 kernel (4 layers: mlp_wide_bwd_kernel; 3: the

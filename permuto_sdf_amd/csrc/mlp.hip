@@ -17,6 +17,7 @@
 #include "psdf_common.h"
 
 #include "mlp_device.h"
+#include "mlp_dispatch.h"
 
 namespace {
 
@@ -372,7 +373,7 @@ int launch_fwd(const MlpPlan& p, int64_t N, const float* X, const float* packed,
                hipStream_t st) {
   const size_t shmem = (size_t)p.total * sizeof(float);
   auto kern = mlp_fwd_kernel<T1, T2, T3, OUT_T, FINAL_DOT>;
-  if (shmem > 160 * 1024) return PSDF_ERR_UNSUPPORTED;
+  if (!fwd_fits(p)) return PSDF_ERR_UNSUPPORTED;
   if (shmem > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return (int)e;
@@ -408,8 +409,7 @@ static int mlp_pack_impl(int n_layers, const int* dims, const float* const* weig
   int rc = make_plan(n_layers, dims, a.plan);
   if (rc != PSDF_OK) return rc;
   // the two-piece fp16 image exists for the net psdf_mlp_forward_f16 is instantiated for
-  if (f16 && !(n_layers == 4 && dims[0] <= 64 && dims[1] == 64 && dims[2] == 64 && dims[3] == 64 && dims[4] <= 4))
-    return PSDF_ERR_UNSUPPORTED;
+  if (f16 && !baseline_split_shape(n_layers, dims, 64, 4)) return PSDF_ERR_UNSUPPORTED;
   for (int l = 0; l < MAXL; l++) {
     a.W[l] = l < n_layers ? weights[l] : nullptr;
     a.b[l] = l < n_layers ? biases[l] : nullptr;
@@ -451,11 +451,13 @@ static int mlp_forward_impl(int n_layers, const int* dims, int64_t N, const floa
   hipStream_t st = (hipStream_t)stream;
   const int t1 = p.tiles[1], t2 = p.tiles[2], t3 = (n_layers == 4) ? p.tiles[3] : 0, to = p.tiles[n_layers];
   if (n_layers != 3 && n_layers != 4) return PSDF_ERR_UNSUPPORTED;
+  if (f16 && !baseline_split_shape(n_layers, dims, 64, 4)) return PSDF_ERR_UNSUPPORTED;   // (the only net psdf_mlp_pack_f16 packs)
   SplitPlan sp;
   make_split_plan(p, sp);
-  // S: shapes whose split-bf16 image can fit SPLIT_LDS_MAX (the wider nets never do, so that kernel is not built for them)
-#define CASE(A, B, C, O, D, S)                                                   \
-  if (t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D) {           \
+  // the rows of PSDF_MLP32_ROWS (mlp_dispatch.h); S: the split-bf16 kernel is built for the row
+#define CASE(A, B, C, O, D, FWD, S, F16)                                        \
+  PSDF_IF(FWD, if (t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D) { \
+    if (f16 && !F16) return PSDF_ERR_UNSUPPORTED;                               \
     if constexpr (S) {                                                          \
       if (sp.ok) {                                                              \
         psdf::g_last_path[psdf::PATH_MLP_FWD] = f16 ? 3 : 2;                    \
@@ -465,14 +467,8 @@ static int mlp_forward_impl(int n_layers, const int* dims, int64_t N, const floa
     if (f16) return PSDF_ERR_UNSUPPORTED;                                       \
     psdf::g_last_path[psdf::PATH_MLP_FWD] = 1;                                  \
     return launch_fwd<A, B, C, O, D>(p, N, X, packed, skip, Y, st);             \
-  }
-  CASE(2, 2, 2, 1, true, true)    // 64x3 -> 1..4      (BASELINE SDF net)
-  CASE(1, 1, 1, 1, true, true)    // 32x3 -> 1..4
-  CASE(1, 1, 1, 2, false, true)   // 32x3 -> 33        (reference SDF net, models.py:153-161)
-  CASE(2, 2, 2, 3, false, false)  // 64x3 -> 65        (background density+feature net, models.py:451-459)
-  CASE(2, 2, 2, 2, false, false)  // 64x3 -> 33
-  CASE(2, 2, 0, 1, true, true)    // 64x2 -> 3         (background colour head, models.py:463-469)
-  CASE(4, 4, 2, 1, true, false)   // 128,128,64 -> 3   (colour net, models.py:350)
+  })
+  PSDF_MLP32_ROWS(CASE)
 #undef CASE
   return PSDF_ERR_UNSUPPORTED;
 }

@@ -30,6 +30,7 @@
 //   Plan16 (row stride 65) is only the layout of the GRADIENT image the workgroup flushes at the end.
 #include <cstdlib>
 #include "mlp_device.h"
+#include "mlp_dispatch.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1186,13 +1187,20 @@ __global__ void __launch_bounds__(BW * 64)
   BWD_STAMP(5);
 }
 
+// LDS of a single-wave launch: the weight image, and per wave the transpose scratch and `stage` (2: backward, 4: double
+// backward) staging buffers of the layer-0 operand.  The launchers and psdf_mlp_supported decline beyond MLP_LDS_MAX.
+template <int TI0, int T1, int T2, int T3, int OUT_T, bool FINAL_DOT>
+size_t bwd_lds_bytes(const Plan16& p, int waves, int stage) {
+  using IM = Img<TI0, T1, T2, T3, FINAL_DOT ? 1 : OUT_T, FINAL_DOT>;
+  const int img = IM::TOTAL > p.total ? IM::TOTAL : ((p.total + 3) & ~3);
+  return ((size_t)img + waves * (16 * 17 + 16 + stage * 4 * TI0 * 64)) * sizeof(float);
+}
+
 template <int TI0, int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, bool Y2 = false>
 int launch_dbl_bwd(const Plan16& p, int64_t N, const float* X, const float* V, const float* dY, float* dX2,
                    const BwdPtrs& a, hipStream_t st, const float* dY2 = nullptr) {
-  using IM = Img<TI0, T1, T2, T3, FINAL_DOT ? 1 : OUT_T, FINAL_DOT>;
-  const int img = IM::TOTAL > p.total ? IM::TOTAL : ((p.total + 3) & ~3);
-  const size_t shmem = ((size_t)img + BW * (16 * 17 + 16 + 4 * 4 * TI0 * 64)) * sizeof(float);
-  if (shmem > 160 * 1024) return PSDF_ERR_UNSUPPORTED;
+  const size_t shmem = bwd_lds_bytes<TI0, T1, T2, T3, OUT_T, FINAL_DOT>(p, BW, 4);
+  if (shmem > MLP_LDS_MAX) return PSDF_ERR_UNSUPPORTED;
   const int64_t ntiles = (N + 15) / 16;
   int64_t blocks = (ntiles + BW - 1) / BW;
   if (blocks > 256) blocks = 256;
@@ -1210,19 +1218,17 @@ int launch_dbl_bwd(const Plan16& p, int64_t N, const float* X, const float* V, c
 // WITH_DW = false: only the data-gradient instantiation exists for this shape.  The 64-wide nets with MANY outputs take their
 // parameter gradients from the workgroup-cooperative kernel (mlp_wide.hip); their single-wave dW instantiations spilled 128 - 253
 // registers and were reachable only while a stream was being captured -- they are not built any more (round 4): such a call
-// returns PSDF_ERR_UNSUPPORTED (tests/test_dispatch_tables.py lists every instantiation that still spills, with its route).
+// returns PSDF_ERR_UNSUPPORTED (the DW column of PSDF_MLP16_ROWS in mlp_dispatch.h: which rows have the dW form).
 template <int TI0, int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, bool WITH_DW, int NW_>
 int launch_bwd_nw(const Plan16& p, int64_t N, const float* X, const float* dY, float* dX, const BwdPtrs& a, hipStream_t st) {
   constexpr int NW = NW_;   // waves per workgroup (launch_bwd below picks it)
   const int64_t ntiles = (N + 15) / 16;
   int64_t blocks = (ntiles + NW - 1) / NW;
   if (blocks > 256) blocks = 256;  // one workgroup per CU; each wave walks many tiles
-  using IM = Img<TI0, T1, T2, T3, FINAL_DOT ? 1 : OUT_T, FINAL_DOT>;
-  const int img = IM::TOTAL > p.total ? IM::TOTAL : ((p.total + 3) & ~3);
   if (!a.dW[0]) {  // data gradient only: no accumulators -> two workgroups per CU
     if (!dX) return PSDF_OK;
-    const size_t shmem = ((size_t)img + BW * (16 * 17 + 16 + 2 * 4 * TI0 * 64)) * sizeof(float);
-    if (shmem > 160 * 1024) return PSDF_ERR_UNSUPPORTED;
+    const size_t shmem = bwd_lds_bytes<TI0, T1, T2, T3, OUT_T, FINAL_DOT>(p, BW, 2);
+    if (shmem > MLP_LDS_MAX) return PSDF_ERR_UNSUPPORTED;
     auto kern = mlp_bwd_kernel<TI0, T1, T2, T3, OUT_T, FINAL_DOT, true, false, BW>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return (int)e;
@@ -1239,8 +1245,8 @@ int launch_bwd_nw(const Plan16& p, int64_t N, const float* X, const float* dY, f
   if constexpr (!WITH_DW) {
     return PSDF_ERR_UNSUPPORTED;
   } else {
-  const size_t shmem = ((size_t)img + NW * (16 * 17 + 16 + 2 * 4 * TI0 * 64)) * sizeof(float);
-  if (shmem > 160 * 1024) return PSDF_ERR_UNSUPPORTED;
+  const size_t shmem = bwd_lds_bytes<TI0, T1, T2, T3, OUT_T, FINAL_DOT>(p, NW, 2);
+  if (shmem > MLP_LDS_MAX) return PSDF_ERR_UNSUPPORTED;
 #define GO(DX)                                                                                                     \
   do {                                                                                                             \
     auto kern = mlp_bwd_kernel<TI0, T1, T2, T3, OUT_T, FINAL_DOT, DX, true, NW>;                                    \
@@ -1292,7 +1298,7 @@ int mlp_backward_head_redo(const int* dims, int64_t N, const float* X, const flo
   Plan16 p;
   int rc = make_plan16(3, dims, p);
   if (rc != PSDF_OK) return rc;
-  if (p.tiles[0] != 5 || p.tiles[1] != 4 || p.tiles[2] != 4 || p.tiles[3] != 1 || !p.final_dot) return PSDF_ERR_UNSUPPORTED;
+  if (!colour_head_shape(3, dims)) return PSDF_ERR_UNSUPPORTED;
   BwdPtrs a;
   for (int l = 0; l < MAXL; l++) {
     a.W[l] = l < 3 ? weights[l] : nullptr;
@@ -1374,19 +1380,9 @@ int psdf_mlp_backward(int n_layers, const int* dims, int64_t N, const float* X, 
   hipStream_t st = (hipStream_t)stream;
   const int ti0 = p.tiles[0], t1 = p.tiles[1], t2 = p.tiles[2], t3 = (n_layers == 4) ? p.tiles[3] : 0,
             to = p.tiles[n_layers];
-  // 64-wide nets with MANY outputs (the background density / feature net 52 -> 64 x 3 -> 65, and 64 x 3 -> 33): their dW does
-  // not fit one wave's registers (the single-wave instantiations below spill 213-227 registers) -- the workgroup-cooperative
-  // kernel of mlp_wide.hip splits the dW rows over 8 waves.  -2 (no stream-ordered scratch: capture) falls through.
-  if (dW && n_layers == 4 && to >= 2 && t1 == 4 && t2 == 4 && t3 == 4) {
-    const int r = psdf_mlp_backward_wide(n_layers, dims, N, X, weights, biases, dY, dX, dW, db, stream);
-    if (r != PSDF_ERR_UNSUPPORTED) {
-      psdf::g_last_path[psdf::PATH_MLP_BWD] = 3;
-      return r;
-    }
-  }
   // the background colour head 80 -> 64 x 2 -> 3: the split-fp16 workgroup kernel, two hidden layers (round 6; the fp32 single-wave
   // instantiation below stays for PSDF_MLP_WIDE_SPLIT=f32, capture, and after an overflow of the fp16 range guard)
-  if (dW && dX && n_layers == 3 && ti0 == 5 && t1 == 4 && t2 == 4 && to == 1 && p.final_dot) {
+  if (dW && dX && colour_head_shape(n_layers, dims)) {
     const int r = psdf_mlp_backward_wide(n_layers, dims, N, X, weights, biases, dY, dX, dW, db, stream);
     if (r != PSDF_ERR_UNSUPPORTED) {
       psdf::g_last_path[psdf::PATH_MLP_BWD] = 3;
@@ -1394,26 +1390,23 @@ int psdf_mlp_backward(int n_layers, const int* dims, int64_t N, const float* X, 
     }
   }
   psdf::g_last_path[psdf::PATH_MLP_BWD] = 1;
-#define CASE_(I, A, B, C, O, D, W)                                               \
-  if (ti0 == I && t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D) \
-    return launch_bwd<I, A, B, C, O, D, W>(p, N, X, dY, dX, a, st);
-#define CASE(I, A, B, C, O, D) CASE_(I, A, B, C, O, D, true)
-#define CASE_DX_ONLY(I, A, B, C, O, D) CASE_(I, A, B, C, O, D, false)
-  CASE(3, 4, 4, 4, 1, true)   // 33..48 -> 64x3 -> 1..4   (BASELINE SDF net on a 16-level encoding)
-  CASE(4, 4, 4, 4, 1, true)   // 49..64 -> 64x3 -> 1..4   (24-level encoding)
-  CASE(2, 4, 4, 4, 1, true)   // 17..32 -> 64x3 -> 1..4   (small encodings)
-  CASE(4, 2, 2, 2, 1, true)   // 49..64 -> 32x3 -> 1..4
-  CASE(3, 2, 2, 2, 1, true)   // 33..48 -> 32x3 -> 1..4
-  CASE(2, 2, 2, 2, 1, true)   // 17..32 -> 32x3 -> 1..4
-  CASE(4, 2, 2, 2, 3, false)  // 52 -> 32x3 -> 33         (reference SDF net, models.py:153-161)
-  CASE(3, 2, 2, 2, 3, false)  // 36 -> 32x3 -> 33         (same net on a 16-level encoding)
-  CASE_DX_ONLY(4, 4, 4, 4, 5, false)  // 52 -> 64x3 -> 65  (background density net, models.py:451-459): dX here, dW in mlp_wide.hip
-  CASE_DX_ONLY(4, 4, 4, 4, 3, false)  // 52 -> 64x3 -> 33
-  CASE_DX_ONLY(3, 4, 4, 4, 3, false)  // 36 -> 64x3 -> 33
-  CASE(5, 4, 4, 0, 1, true)   // 80 -> 64x2 -> 3          (background colour head, models.py:463-469)
+  // PSDF_MLP16_ROWS (mlp_dispatch.h).  A row without the DW column (the 64-wide nets with MANY outputs: their single-wave dW spills
+  // 213-227 registers) takes its parameter gradients from the workgroup-cooperative kernel of mlp_wide.hip, which splits the dW
+  // rows over 8 waves; -2 from there (no stream-ordered scratch: capture) reaches the data-gradient-only launcher, which declines.
+#define CASE(I, A, B, C, O, D, DW, DX, MASKED, DBL, PLUS)                                        \
+  if (ti0 == I && t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D) {               \
+    if (!DX && !dW) return PSDF_ERR_UNSUPPORTED;                                                \
+    if (!DW && dW) {                                                                            \
+      const int r = psdf_mlp_backward_wide(n_layers, dims, N, X, weights, biases, dY, dX, dW, db, stream); \
+      if (r != PSDF_ERR_UNSUPPORTED) {                                                          \
+        psdf::g_last_path[psdf::PATH_MLP_BWD] = 3;                                              \
+        return r;                                                                               \
+      }                                                                                         \
+    }                                                                                           \
+    return launch_bwd<I, A, B, C, O, D, DW != 0>(p, N, X, dY, dX, a, st);                       \
+  }
+  PSDF_MLP16_ROWS(CASE)
 #undef CASE
-#undef CASE_DX_ONLY
-#undef CASE_
   // nets too wide for one wave's registers (the 128-wide colour network): workgroup-cooperative kernel, mlp_wide.hip
   psdf::g_last_path[psdf::PATH_MLP_BWD] = 3;
   if (dW) return psdf_mlp_backward_wide(n_layers, dims, N, X, weights, biases, dY, dX, dW, db, stream);
@@ -1431,6 +1424,49 @@ int psdf_mlp_backward(int n_layers, const int* dims, int64_t N, const float* X, 
 int psdf_last_path(int family) {
   if (family < 0 || family >= psdf::PATH_FAMILIES) return -1;
   return psdf::g_last_path[family];
+}
+
+// include/psdf.h.  Answers what the dispatchers above, mlp_forward_impl (mlp.hip) and the mlp_wide.hip entries do for
+// these widths, from the same table rows, shape predicates and LDS checks; the single-wave dW launch is sized for one wave
+// per SIMD (launch_bwd: what small batches get).
+int psdf_mlp_supported(int op, int n_layers, const int* dims) {
+  MlpPlan p;
+  Plan16 q;
+  if (op < PSDF_MLP_OP_FORWARD || op > PSDF_MLP_OP_DOUBLE_BACKWARD_PLUS || !dims || make_plan(n_layers, dims, p) != PSDF_OK ||
+      make_plan16(n_layers, dims, q) != PSDF_OK)
+    return PSDF_ERR_ARG;
+  if (op == PSDF_MLP_OP_FORWARD_WIDE_F16) return colour_net_shape(n_layers, dims) || density_net_shape(n_layers, dims);
+  if (n_layers != 3 && n_layers != 4) return 0;
+  if (op == PSDF_MLP_OP_FORWARD || op == PSDF_MLP_OP_FORWARD_F16) {
+    const bool f16 = op == PSDF_MLP_OP_FORWARD_F16;
+    if (f16 && !baseline_split_shape(n_layers, dims, 64, 4)) return 0;
+    SplitPlan sp;
+    make_split_plan(p, sp);
+    const int t1 = p.tiles[1], t2 = p.tiles[2], t3 = (n_layers == 4) ? p.tiles[3] : 0, to = p.tiles[n_layers];
+#define ROW(A, B, C, O, D, FWD, S, F16)                                                            \
+    if (FWD && t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D)                       \
+      return (S && sp.ok) ? (!f16 || F16) : (!f16 && fwd_fits(p));
+    PSDF_MLP32_ROWS(ROW)
+#undef ROW
+    return 0;
+  }
+  const int ti0 = q.tiles[0], t1 = q.tiles[1], t2 = q.tiles[2], t3 = (n_layers == 4) ? q.tiles[3] : 0, to = q.tiles[n_layers];
+#define ROW(I, A, B, C, O, D, DW, DX, MASKED, DBL, PLUS)                                           \
+  if (ti0 == I && t1 == A && t2 == B && t3 == C && to == O && q.final_dot == D) {                  \
+    const bool bwd = bwd_lds_bytes<I, A, B, C, O, D>(q, BW, 2) <= MLP_LDS_MAX;                     \
+    const bool dbl = bwd_lds_bytes<I, A, B, C, O, D>(q, BW, 4) <= MLP_LDS_MAX;                     \
+    switch (op) {                                                                                  \
+      case PSDF_MLP_OP_BACKWARD: return DW ? bwd : wide_backward_shape(n_layers, dims);            \
+      case PSDF_MLP_OP_BACKWARD_DATA: return DX && bwd;                                            \
+      case PSDF_MLP_OP_BACKWARD_DATA_MASKED: return MASKED && bwd;                                 \
+      case PSDF_MLP_OP_DOUBLE_BACKWARD: return DBL && dbl;                                         \
+      default: return PLUS && dbl;                                                                 \
+    }                                                                                              \
+  }
+  PSDF_MLP16_ROWS(ROW)
+#undef ROW
+  // no single-wave row: psdf_mlp_backward hands parameter-gradient calls to psdf_mlp_backward_wide
+  return op == PSDF_MLP_OP_BACKWARD && wide_backward_shape(n_layers, dims);
 }
 
 // psdf_mlp_backward restricted to the data gradient (dW = db = NULL) with a per-sample mask: 16-sample tiles whose samples
@@ -1457,15 +1493,10 @@ int psdf_mlp_backward_data_masked(int n_layers, const int* dims, int64_t N, cons
   hipStream_t st = (hipStream_t)stream;
   const int ti0 = p.tiles[0], t1 = p.tiles[1], t2 = p.tiles[2], t3 = (n_layers == 4) ? p.tiles[3] : 0,
             to = p.tiles[n_layers];
-#define CASE(I, A, B, C, O, D)                                                   \
-  if (ti0 == I && t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D) \
-    return launch_bwd<I, A, B, C, O, D>(p, N, X, dY, dX, a, st);
-  CASE(3, 4, 4, 4, 1, true)
-  CASE(4, 4, 4, 4, 1, true)
-  CASE(2, 4, 4, 4, 1, true)
-  CASE(4, 2, 2, 2, 1, true)
-  CASE(3, 2, 2, 2, 1, true)
-  CASE(2, 2, 2, 2, 1, true)
+#define CASE(I, A, B, C, O, D, DW, DX, MASKED, DBL, PLUS)                                        \
+  PSDF_IF(MASKED, if (ti0 == I && t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D) \
+    return launch_bwd<I, A, B, C, O, D>(p, N, X, dY, dX, a, st);)
+  PSDF_MLP16_ROWS(CASE)
 #undef CASE
   return PSDF_ERR_UNSUPPORTED;
 }
@@ -1493,24 +1524,16 @@ static int mlp_double_backward_impl(int n_layers, const int* dims, int64_t N, co
   }
   hipStream_t st = (hipStream_t)stream;
   const int ti0 = p.tiles[0], t1 = p.tiles[1], t2 = p.tiles[2], t3 = p.tiles[3], to = p.tiles[n_layers];
-#define CASE(I, A, B, C, O, D)                                                   \
-  if (ti0 == I && t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D) \
-    return launch_dbl_bwd<I, A, B, C, O, D>(p, N, X, V, dY, dX2, a, st);
-  if (dY2) {     // with the plain backward of an upstream gradient of the outputs folded in: the reference's SDF net only
-    if (ti0 == 4 && t1 == 2 && t2 == 2 && t3 == 2 && to == 3 && !p.final_dot)
-      return launch_dbl_bwd<4, 2, 2, 2, 3, false, true>(p, N, X, V, dY, dX2, a, st, dY2);
-    if (ti0 == 3 && t1 == 2 && t2 == 2 && t3 == 2 && to == 3 && !p.final_dot)
-      return launch_dbl_bwd<3, 2, 2, 2, 3, false, true>(p, N, X, V, dY, dX2, a, st, dY2);
-    return PSDF_ERR_UNSUPPORTED;
-  }
-  CASE(4, 2, 2, 2, 3, false)  // 52 -> 32x3 -> 33   (reference SDF net, models.py:153-161)
-  CASE(3, 2, 2, 2, 3, false)  // 36 -> 32x3 -> 33
-  CASE(4, 2, 2, 2, 1, true)   // 49..64 -> 32x3 -> 1..4
-  CASE(3, 2, 2, 2, 1, true)
-  CASE(2, 2, 2, 2, 1, true)
-  CASE(3, 4, 4, 4, 1, true)   // 36 -> 64x3 -> 1..4 (BASELINE net)
-  CASE(4, 4, 4, 4, 1, true)
+  // PSDF_MLP16_ROWS: the DBL rows, or with the plain backward of an upstream gradient of the outputs folded in (dY2) the PLUS rows
+#define MATCH(I, A, B, C, O, D) (ti0 == I && t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D)
+#define CASE(I, A, B, C, O, D, DW, DX, MASKED, DBL, PLUS)                                        \
+  PSDF_IF(PLUS, if (dY2 && MATCH(I, A, B, C, O, D))                                            \
+    return launch_dbl_bwd<I, A, B, C, O, D, true>(p, N, X, V, dY, dX2, a, st, dY2);)           \
+  PSDF_IF(DBL, if (!dY2 && MATCH(I, A, B, C, O, D))                                            \
+    return launch_dbl_bwd<I, A, B, C, O, D>(p, N, X, V, dY, dX2, a, st);)
+  PSDF_MLP16_ROWS(CASE)
 #undef CASE
+#undef MATCH
   return PSDF_ERR_UNSUPPORTED;
 }
 

@@ -18,6 +18,7 @@
 // -mllvm -amdgpu-mfma-vgpr-form=1 (only the accumulators live in AGPRs); the K0 <= 36 instantiation in its own translation
 // unit (mlp_bwd_split_double.hip).
 #include "psdf_common.h"
+#include "mlp_dispatch.h"
 
 namespace {
 
@@ -681,10 +682,8 @@ size_t psdf::mlp_backward_split_scratch_bytes(int K0, int64_t N) {
 int psdf::mlp_backward_split_impl(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
                                   const float* const* biases, const float* dY, float* dX, float* const* dW, float* const* db,
                                   hipStream_t st, char* scratch, const uint32_t* only_if) {
-  if (n_layers != 4 || !dims || dims[1] != HID || dims[2] != HID || dims[3] != HID || dims[4] != 1 || !dW || !db)
-    return PSDF_ERR_UNSUPPORTED;
+  if (!dims || !dW || !db || !baseline_split_shape(n_layers, dims, 64, 1)) return PSDF_ERR_UNSUPPORTED;
   const int K0 = dims[0];
-  if (K0 < 1 || K0 > 64) return PSDF_ERR_UNSUPPORTED;
   const int rows4 = (K0 + 3) & ~3;
   const int nt0 = K0 <= 48 ? 3 : 4;
   const size_t stage_bytes = (size_t)NWAVES * (rows4 * 16 + 64) * 4;

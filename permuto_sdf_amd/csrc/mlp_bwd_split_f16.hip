@@ -37,6 +37,7 @@
 // Accuracy against float64: tests/test_gpu_mlp.py::test_split_f16_backward_matches_float64.  Built with
 // -mllvm -amdgpu-mfma-vgpr-form=1 -fno-slp-vectorize (build.py).
 #include "psdf_common.h"
+#include "mlp_dispatch.h"
 #include <stdio.h>
 #include <type_traits>
 #include <stdlib.h>
@@ -869,10 +870,8 @@ int psdf_mlp_backward_split_f16_form(void) { return g_f16_form; }
 int psdf_mlp_backward_split_f16(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
                                 const float* const* biases, const float* dY, float* dX, float* const* dW, float* const* db,
                                 void* stream) {
-  if (n_layers != 4 || !dims || dims[1] != HID || dims[2] != HID || dims[3] != HID || dims[4] != 1 || !dW || !db)
-    return PSDF_ERR_UNSUPPORTED;
+  if (!dims || !dW || !db || !baseline_split_shape(n_layers, dims, 64, 1)) return PSDF_ERR_UNSUPPORTED;
   const int K0 = dims[0];
-  if (K0 < 1 || K0 > 64) return PSDF_ERR_UNSUPPORTED;
   const int rows4 = (K0 + 3) & ~3;
   const int nt0 = K0 <= 48 ? 3 : 4;
   const size_t stage_bytes = (size_t)NWAVES * (64 * 16 + 64) * 4;

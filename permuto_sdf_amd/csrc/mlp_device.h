@@ -50,6 +50,11 @@ static int make_plan(int n_layers, const int* dims, MlpPlan& p) {
   return PSDF_OK;
 }
 
+constexpr size_t MLP_LDS_MAX = 160 * 1024;  // dynamic LDS a single-wave MLP launch may ask for
+
+// the fp32 forward (mlp_fwd_kernel) stages the whole packed image; launch_fwd and psdf_mlp_supported decline beyond MLP_LDS_MAX
+inline bool fwd_fits(const MlpPlan& p) { return (size_t)p.total * sizeof(float) <= MLP_LDS_MAX; }
+
 // -------------------------------------------------------------------------------------- device math
 // erf with < 1 ulp error, branch-free (both ranges evaluated, then selected): a ~20-instruction VALU
 // sequence instead of the two-branch library erff, which matters because 96 GELUs per lane sit between

@@ -17,6 +17,7 @@
 //     kernel is latency / launch bound, not matrix bound.
 // One barrier per layer and direction (8 per tile).
 #include "psdf_common.h"
+#include "mlp_dispatch.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <atomic>
@@ -1495,8 +1496,8 @@ int wide_forward_f16(const int* dims, int64_t N, const float* X, const float* co
 
 extern "C" {
 
-// Forward of the colour network's shape (dims[0] <= 112, dims[1], dims[2] <= 128, dims[3] <= 64, dims[4] <= 16, not both hidden widths
-// <= 64; GELU between the layers, the last one linear) on the fp16 matrix pipe with two pieces per fp32 operand (round 6): X
+// Forward of the colour network's shape (colour_net_shape, mlp_dispatch.h) and of the background density net 52 -> 64 x 3 -> 65
+// (density_net_shape), GELU between the layers, the last one linear, on the fp16 matrix pipe with two pieces per fp32 operand (round 6): X
 // [dims[0], N] and Y [dims[4], N] feature-major, weights[l] / biases[l] the torch-layout parameters (for a LipshitzMLP: the NORMALISED
 // weights).  -2 for other shapes, while a stream is being captured, and after a value beyond the fp16 range was met
 // (psdf_mlp_forward evaluates every shape in fp32).  Replaces the torch.nn / LipshitzMLP forward of models.py:54-129,349-350.
@@ -1511,11 +1512,8 @@ int psdf_mlp_forward_wide_f16(int n_layers, const int* dims, int64_t N, const fl
   if (sp && sp[0] == 'f' && sp[1] == '3') return PSDF_ERR_UNSUPPORTED;
   uint32_t* ov = wide_overflow_word();
   if (ov && *(volatile uint32_t*)ov) return PSDF_ERR_UNSUPPORTED;
-  if (dims[0] <= 112 && dims[1] <= 128 && dims[2] <= 128 && dims[3] <= 64 && dims[4] <= 16 && !(dims[1] <= 64 && dims[2] <= 64))
-    return wide_forward_f16<7, 8, 8, 4, 1>(dims, N, X, weights, biases, Y, (hipStream_t)stream);
-  // the background density / feature net 52 -> 64 x 3 -> 65 (models.py:451-459)
-  if (dims[0] <= 64 && dims[1] > 32 && dims[1] <= 64 && dims[2] > 32 && dims[2] <= 64 && dims[3] > 32 && dims[3] <= 64 &&
-      dims[4] > 16 && dims[4] <= 80)
+  if (colour_net_shape(n_layers, dims)) return wide_forward_f16<7, 8, 8, 4, 1>(dims, N, X, weights, biases, Y, (hipStream_t)stream);
+  if (density_net_shape(n_layers, dims))
     return wide_forward_f16<4, 4, 4, 4, 5>(dims, N, X, weights, biases, Y, (hipStream_t)stream);
   return PSDF_ERR_UNSUPPORTED;
 }
@@ -1579,12 +1577,10 @@ int psdf_lipshitz_normalize_backward_multi(int n_layers, const int* out, const i
   return PSDF_OK;
 }
 
-// Same contract as psdf_mlp_backward (include/psdf.h) for 4-layer nets whose dW does not fit one wave's registers:
-//   * dims[0] <= 112, dims[1], dims[2] <= 128, dims[3] <= 64, dims[4] <= 16 (not both hidden widths <= 64): the reference's colour
-//     network, LipshitzMLP 111 -> 128 -> 128 -> 64 -> 3 (models.py:349-350);
-//   * dims[0..3] <= 64, 16 < dims[4] <= 80: the background density / feature net 52 -> 64 x 3 -> 65 (models.py:451-459) and
-//     64 x 3 -> 33 (round 3);
-// -2 otherwise.
+// Same contract as psdf_mlp_backward (include/psdf.h) for nets whose dW does not fit one wave's registers (wide_backward_shape,
+// mlp_dispatch.h): the reference's colour network, LipshitzMLP 111 -> 128 -> 128 -> 64 -> 3 (models.py:349-350); the background
+// density / feature net 52 -> 64 x 3 -> 65 (models.py:451-459) and 64 x 3 -> 33 (round 3); the background colour head
+// 80 -> 64 -> 64 -> 3.  -2 otherwise.
 int psdf_mlp_backward_wide(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
                            const float* const* biases, const float* dY, float* dX, float* const* dW, float* const* db,
                            void* stream) {
@@ -1603,7 +1599,7 @@ int psdf_mlp_backward_wide(int n_layers, const int* dims, int64_t N, const float
       g_wide_form = 1;        // (the caller's single-wave fp32 kernel takes the call)
       return PSDF_ERR_UNSUPPORTED;
     }
-    if (dims[0] > 64 && dims[0] <= 80 && dims[1] > 32 && dims[1] <= 64 && dims[2] > 32 && dims[2] <= 64 && dims[3] <= 4) {
+    if (colour_head_shape(n_layers, dims)) {
       g_wide_form = 2;
       return wide_launch_f16<5, 4, 4, 0, 1>(3, dims, N, X, weights, biases, dY, dX, dW, db, st);
     }
@@ -1625,7 +1621,7 @@ int psdf_mlp_backward_wide(int n_layers, const int* dims, int64_t N, const float
   }
   g_wide_form = f16 ? 2 : 1;
   // the colour network (111 -> 128 -> 128 -> 64 -> 3) and anything that fits its tile counts with one output tile
-  if (dims[0] <= 112 && dims[1] <= 128 && dims[2] <= 128 && dims[3] <= 64 && dims[4] <= 16 && !(dims[1] <= 64 && dims[2] <= 64)) {
+  if (colour_net_shape(n_layers, dims)) {
     if (f16) {
       const int r = wide_launch_f16<7, 8, 8, 4, 1>(4, dims, N, X, weights, biases, dY, dX, dW, db, st);
       if (r != PSDF_ERR_UNSUPPORTED) return r;
@@ -1633,8 +1629,8 @@ int psdf_mlp_backward_wide(int n_layers, const int* dims, int64_t N, const float
     }
     return wide_launch<7, 8, 8, 4, 1>(dims, N, X, weights, biases, dY, dX, dW, db, st);
   }
-  // the background density / feature net (52 -> 64 x 3 -> 65) and its 33-output sibling: up to 80 outputs, 64-wide hidden layers
-  if (dims[0] <= 64 && dims[1] <= 64 && dims[2] <= 64 && dims[3] <= 64 && dims[4] > 16 && dims[4] <= 80) {
+  // the background density / feature net (52 -> 64 x 3 -> 65) and its 33-output sibling: up to 80 outputs, 33..64-wide hidden layers
+  if (density_net_shape(n_layers, dims)) {
     if (f16) {
       const int r = wide_launch_f16<4, 4, 4, 4, 5>(4, dims, N, X, weights, biases, dY, dX, dW, db, st);
       if (r != PSDF_ERR_UNSUPPORTED) return r;

@@ -26,9 +26,24 @@ def packed_size(dims):
     return int(r)
 
 
+# operations of psdf_mlp_supported (include/psdf.h: PSDF_MLP_OP_*)
+(OP_FORWARD, OP_FORWARD_F16, OP_FORWARD_WIDE_F16, OP_BACKWARD, OP_BACKWARD_DATA, OP_BACKWARD_DATA_MASKED, OP_DOUBLE_BACKWARD,
+ OP_DOUBLE_BACKWARD_PLUS) = range(8)
+_SUPPORTED = {}
+
+
+def supported(op, dims):
+    """True when the library has a fused kernel of `op` for these widths (psdf_mlp_supported: the dispatch table of
+    csrc/mlp_dispatch.h).  Asked once per (op, widths); later calls are a dict lookup."""
+    key = (op, tuple(dims))
+    r = _SUPPORTED.get(key)
+    if r is None:
+        r = _SUPPORTED[key] = L.lib().psdf_mlp_supported(L.c_i(op), L.c_i(len(dims) - 1), _dims_array(dims)) == 1
+    return r
+
+
 def f16_forward_supported(dims):
-    """psdf_mlp_forward_f16 exists for the BASELINE net: <= 64 inputs, 64x3, <= 4 outputs"""
-    return len(dims) == 5 and dims[0] <= 64 and dims[1] == dims[2] == dims[3] == 64 and dims[4] <= 4
+    return supported(OP_FORWARD_F16, dims)
 
 
 def pack_params(dims, weights, biases, f16=False):
@@ -65,17 +80,6 @@ def mlp_forward_raw(dims, x_fm, packed, skip=None, out=None, f16=False):
 
 
 _wide_f16_fn = None
-
-
-def wide_f16_forward_candidate(dims):
-    """the shapes psdf_mlp_forward_wide_f16 is instantiated for (csrc/mlp_wide.hip): the colour network 111-128-128-64-3 and the
-    background density net 52-64-64-64-65; asked before the call so that other nets do not pay an ABI round trip for a -2"""
-    if len(dims) != 5:
-        return False
-    d = dims
-    colour = d[0] <= 112 and d[1] <= 128 and d[2] <= 128 and d[3] <= 64 and d[4] <= 16 and not (d[1] <= 64 and d[2] <= 64)
-    density = d[0] <= 64 and 32 < d[1] <= 64 and 32 < d[2] <= 64 and 32 < d[3] <= 64 and 16 < d[4] <= 80
-    return colour or density
 
 
 def mlp_forward_wide_f16_raw(dims, x_fm, weights, biases, out=None):
@@ -172,17 +176,7 @@ def mlp_backward_raw(dims, x_fm, weights, biases, gy_fm, need_dx=True, need_dw=T
 
 
 def backward_supported(dims):
-    """True when csrc/mlp_bwd.hip has an instantiation for these widths (tile signature, 16-wide tiles)."""
-    n_layers = len(dims) - 1
-    if n_layers not in (3, 4):
-        return False
-    t = [(d + 15) // 16 for d in dims]
-    if n_layers == 4 and t[0] <= 7 and t[1] <= 8 and t[2] <= 8 and t[3] <= 4 and dims[4] <= 16 and (t[1] > 4 or t[2] > 4):
-        return True     # csrc/mlp_wide.hip: the 128-wide colour network (workgroup-cooperative kernel)
-    sig = (t[0], t[1], t[2], t[3] if n_layers == 4 else 0, t[n_layers], dims[-1] <= 4)
-    return sig in {(3, 4, 4, 4, 1, True), (4, 4, 4, 4, 1, True), (2, 4, 4, 4, 1, True), (4, 2, 2, 2, 1, True),
-                   (3, 2, 2, 2, 1, True), (2, 2, 2, 2, 1, True), (4, 2, 2, 2, 3, False), (4, 4, 4, 4, 5, False),
-                   (4, 4, 4, 4, 3, False), (5, 4, 4, 0, 1, True), (3, 2, 2, 2, 3, False), (3, 4, 4, 4, 3, False)}
+    return supported(OP_BACKWARD, dims)
 
 
 _ANNOUNCED = set()
@@ -200,22 +194,16 @@ def torch_fallback_allowed(module=None):
 def _announce(kind, dims, module=None):
     """say ONCE per (operator, widths) that a net is served by torch/rocBLAS on the GPU instead of a fused kernel"""
     if not torch_fallback_allowed(module):
-        raise L.PsdfError("permuto_sdf_amd: no fused %s kernel is instantiated for the MLP widths %s (csrc/mlp_bwd.hip lists the "
-                          "instantiated widths).  Refusing to fall back to torch/rocBLAS silently: pass allow_torch_fallback=True "
+        raise L.PsdfError("permuto_sdf_amd: no fused %s kernel is instantiated for the MLP widths %s (csrc/mlp_dispatch.h lists "
+                          "the instantiated widths).  Refusing to fall back to torch/rocBLAS silently: pass allow_torch_fallback=True "
                           "to FusedMLP or set PSDF_MLP_TORCH_FALLBACK=1 to opt in." % (kind, list(dims)))
     key = (kind, tuple(dims))
     if key not in _ANNOUNCED:
         _ANNOUNCED.add(key)
         import warnings
         warnings.warn("permuto_sdf_amd: no fused %s kernel is instantiated for the MLP widths %s; using torch autograd over "
-                      "rocBLAS on the GPU for it (csrc/mlp_bwd.hip lists the instantiated widths)" % (kind, list(dims)),
+                      "rocBLAS on the GPU for it (csrc/mlp_dispatch.h lists the instantiated widths)" % (kind, list(dims)),
                       RuntimeWarning, stacklevel=3)
-
-
-def dx_only_supported(dims):
-    """the data-gradient-only variant exists for the narrow kernel family (csrc/mlp_bwd.hip), not for mlp_wide.hip"""
-    t = [(d + 15) // 16 for d in dims]
-    return backward_supported(dims) and not (len(dims) == 5 and (t[1] > 4 or t[2] > 4))
 
 
 def _torch_gpu_backward(dims, x_fm, weights, biases, gy_fm, need_dx, module=None):
@@ -302,7 +290,7 @@ class _FusedMLPFunc(torch.autograd.Function):
         if not x_fm.is_contiguous():
             x_fm = x_fm.contiguous()
         y = None
-        if wide_f16_forward_candidate(module.dims):      # colour network / background density net: the fp16 matrix pipe (round 6)
+        if supported(OP_FORWARD_WIDE_F16, module.dims):      # colour network / background density net: the fp16 matrix pipe
             y = mlp_forward_wide_f16_raw(module.dims, x_fm, weights, biases)
         if y is None:
             packed = pack_params(module.dims, weights, biases)
@@ -345,7 +333,7 @@ class _FusedMLPBackFunc(torch.autograd.Function):
         gy_fm = gy.t()
         if not gy_fm.is_contiguous():
             gy_fm = gy_fm.contiguous()
-        if not need_dw and dx_only_supported(module.dims):
+        if not need_dw and supported(OP_BACKWARD_DATA, module.dims):
             dx, dWs, dbs = mlp_backward_raw(module.dims, x_fm, weights, biases, gy_fm, need_dx=need_dx, need_dw=False)
         elif backward_supported(module.dims):
             gb = module.grad_buffer if buffered else None
@@ -398,19 +386,11 @@ class _FusedMLPBackFunc(torch.autograd.Function):
 
 
 def double_backward_supported(dims):
-    """True when csrc/mlp_bwd.hip has a fused double-backward instantiation for these widths"""
-    if len(dims) != 5:
-        return False
-    t = [(d + 15) // 16 for d in dims]
-    sig = (t[0], t[1], t[2], t[3], t[4], dims[-1] <= 4)
-    return sig in {(4, 2, 2, 2, 3, False), (3, 2, 2, 2, 3, False), (4, 2, 2, 2, 1, True), (3, 2, 2, 2, 1, True),
-                   (2, 2, 2, 2, 1, True), (3, 4, 4, 4, 1, True), (4, 4, 4, 4, 1, True)}
+    return supported(OP_DOUBLE_BACKWARD, dims)
 
 
 def double_backward_plus_supported(dims):
-    """psdf_mlp_double_backward_plus: the reference's SDF net shapes (<= 64 inputs, 32 x 3 hidden, matrix output layer <= 48 rows)"""
-    return (len(dims) == 5 and 32 < dims[0] <= 64 and 16 < dims[1] <= 32 and 16 < dims[2] <= 32 and 16 < dims[3] <= 32
-            and 32 < dims[4] <= 48)
+    return supported(OP_DOUBLE_BACKWARD_PLUS, dims)
 
 
 def mlp_double_backward(dims, x_fm, weights, biases, gy_fm, v_fm, into=None, module=None, gy2_fm=None):

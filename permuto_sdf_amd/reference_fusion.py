@@ -26,14 +26,7 @@ from . import mlp as M
 
 
 def forward_supported(dims):
-    """True when csrc/mlp.hip has a forward instantiation for these widths (tiles of 32; the CASE table of mlp_forward_impl)"""
-    n_layers = len(dims) - 1
-    if n_layers not in (3, 4) or dims[0] > 128:
-        return False
-    t = [(d + 31) // 32 for d in dims]
-    sig = (t[1], t[2], t[3] if n_layers == 4 else 0, t[n_layers], dims[-1] <= 4)
-    return sig in {(2, 2, 2, 1, True), (1, 1, 1, 1, True), (1, 1, 1, 2, False), (2, 2, 2, 3, False), (2, 2, 2, 2, False),
-                   (2, 2, 0, 1, True), (4, 4, 2, 1, True)}
+    return M.supported(M.OP_FORWARD, dims)
 
 
 def _is_linear_gelu_stack(seq):
