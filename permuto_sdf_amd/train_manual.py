@@ -2,7 +2,7 @@
 losses, schedule, optimiser, data-parallel reduction -- it IS a Trainer), but the main phase's forward and backward are
 written out over the raw feature-major kernels instead of being recorded and replayed by torch autograd.
 
-Why: the step is host bound (train_step.py): ~250 launches, the autograd engine's bookkeeping
+Why: the step is host bound (train_step.py, DESIGN.md sections 4.5 and 8): ~250 launches, the autograd engine's bookkeeping
 (`run_backward` alone is a third of the host time), [N, C] <-> [C, N] glue around every Function, gradient-accumulation adds
 and zero fills that autograd inserts.  Written by hand, every tensor stays feature-major, every gradient is produced once where
 it is needed, the three evaluations of the SDF network share one parameter image, and the four contributions to the SDF
@@ -17,9 +17,12 @@ The backward of  n = d sdf / d p  is the double backward: `psdf_encode_double_ba
 the feature gradient) -> `psdf_mlp_double_backward` (gradient w.r.t. features and parameters) -> the encoding's lattice backward.
 `tests/test_gpu_train_step.py::test_manual_backward_equals_autograd` holds every gradient of this file against the autograd
 trainer's on the same batch.
+
+Layout: `_main_phase` = `_main_forward` (sampling, every forward, every loss kernel, grid refresh, prefetch) -> a `_Step` record
+-> `_main_backward`; each half is a sequence of stages (`_fg_forward` / `_fg_backward`, `_curvature_*`, `_offsurface_*`, `_calib_*`).
 """
-import contextlib
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -87,13 +90,50 @@ def _set_grads(layers, dWs, dbs):
         l.weight.grad, l.bias.grad = dW, db
 
 
+def _net(mlp):
+    """(dims, layers, weights, biases) of an MLP module as the raw kernels take them"""
+    layers = list(mlp.layers)
+    return mlp.dims, layers, [l.weight for l in layers], [l.bias for l in layers]
+
+
+class _Step:
+    """What `_main_forward` hands to `_main_backward`: every field exists from the start, None until its stage has run, so the
+    backward tests the field (calib, g_cw_bg, g_cb_bg: colour calibration; fg, g_n: foreground samples; curv: curvature weight
+    > 0) and not the condition the forward ran under.  calib, net, bg, fg, curv are small records (SimpleNamespace), each built
+    in one place: `_calib_build`, `_main_forward`, `_bg_forward`, `_fg_forward`, `_curvature_forward`."""
+    __slots__ = ("it", "R", "n_fg", "loss", "calib", "net", "inv_s", "cos_r", "arena", "bg", "fg", "curv", "off", "feat_o",
+                 "g_pred", "g_bgT", "g_n", "g_cw_bg", "g_cb_bg")
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw.pop(name, None))
+        assert not kw, kw
+
+
+def _calib_sigmoid(calib, raw_fm, ray_start_end_idx):
+    """[3, N] raw colours -> ((calibrated) sigmoid [N, 3], raw colours [N, 3], ray of each sample [N]); the last two with
+    calibration only"""
+    if calib is None:
+        return sigmoid_rows_raw(raw_fm), None, None
+    raw = raw_fm.t().contiguous()
+    ridx = RaySamplesPacked.compute_per_sample_ray_idx(ray_start_end_idx, raw.shape[0]).long()
+    return torch.sigmoid(raw * calib.cw.index_select(0, ridx) + calib.cb.index_select(0, ridx)), raw, ridx
+
+
+def _calib_sigmoid_backward(calib, g_rgb, rgb, raw, ridx):
+    """-> (gradient of the raw colours [3, N], g_cw [R, 3], g_cb [R, 3]); the last two None without calibration"""
+    if calib is None:
+        return sigmoid_rows_backward_raw(g_rgb, rgb), None, None                         # one launch
+    g_pre = g_rgb * rgb * (1.0 - rgb)                                                     # sigmoid
+    g_cb = torch.zeros(calib.cb.shape, device=g_pre.device).index_add_(0, ridx, g_pre)
+    g_cw = torch.zeros(calib.cb.shape, device=g_pre.device).index_add_(0, ridx, g_pre * raw)
+    return (g_pre * calib.cw.index_select(0, ridx)).t().contiguous(), g_cw, g_cb
+
+
 class ManualTrainer(Trainer):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         assert self.touched, "ManualTrainer accumulates the lattice gradients in the touched-rows buffers"
-        # second stream for the background branch: OFF by default -- measured slower (see _main_phase); PSDF_TRAIN_STREAMS=1 turns it on
-        self.overlap_streams = os.environ.get("PSDF_TRAIN_STREAMS", "0") == "1"
-        self._side = None
         self._g_yo = None
         # the NEXT step's rays, sphere intersection, occupancy march and background samples are issued on a side stream as soon
         # as this step's grid refresh is enqueued, and run beside this step's backward (PSDF_TRAIN_PREFETCH=0: off)
@@ -103,12 +143,6 @@ class ManualTrainer(Trainer):
         self._pos_pool = None
         # the SDF net's plain backward (g_y) inside the double backward's launch (g_n); PSDF_TRAIN_FUSE_SDF_BWD=0: two launches
         self.fuse_sdf_backward = os.environ.get("PSDF_TRAIN_FUSE_SDF_BWD", "1") != "0"
-        self._events = [torch.cuda.Event() for _ in range(4)] if self.dev.type == "cuda" else []
-
-    def _side_stream(self):
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.dev)
-        return self._side
 
     # ------------------------------------------------------------------ next step's sampling, first half, ahead of time
     def _prefetch_valid(self, git, reel=None):
@@ -178,12 +212,11 @@ class ManualTrainer(Trainer):
                 and hp.max_nr_samples_per_ray + 2 * hp.nr_samples_imp_sampling <= 256)
 
     # ------------------------------------------------------------------ the SDF network, one evaluation
-    def _sdf_gradient(self, feat, pts, win, ws, bs):
+    def _sdf_gradient(self, feat, pts, net):
         """n = d sdf / d p and the feature gradient it came through"""
-        dims = self.sdf.mlp_sdf.dims
         e0 = None       # "the unit gradient of output 0": the kernels take NULL for it (no [33, N] tensor that is 1 in one row)
-        dfeat, _, _ = mlp_backward_raw(dims, feat, ws, bs, e0, need_dx=True, need_dw=False)
-        n = _enc_bwd(self.sdf.encoding, pts, win, dfeat, want_pos=True, want_lattice=False, zeroed=self._zeroed_pos(pts))
+        dfeat, _, _ = mlp_backward_raw(net.dims, feat, net.ws, net.bs, e0, need_dx=True, need_dw=False)
+        n = _enc_bwd(self.sdf.encoding, pts, net.win, dfeat, want_pos=True, want_lattice=False, zeroed=self._zeroed_pos(pts))
         return n, dfeat, e0
 
     def _zeroed_pos(self, pts):
@@ -213,14 +246,15 @@ class ManualTrainer(Trainer):
         views = [_grad_views(d, flat=flat[offs[i]:offs[i + 1]])[1:] for i, d in enumerate((d1, d2, dc))]
         return views[0], views[1], views[2], flat[offs[3]:offs[4]]
 
-    def _sdf_gradient_backward(self, g_n, feat, dfeat, e0, pts, win, ws, bs, gb, want_pos=False, extra_dfeat=None, extra_gy=None):
+    def _sdf_gradient_backward(self, g_n, feat, dfeat, e0, pts, net, want_pos=False, extra_dfeat=None, extra_gy=None):
         """backward of  n = d sdf / d p  for an upstream g_n [N,3]: lattice and parameter gradients are accumulated; returns the
         position gradient when asked (the shifted points of the curvature term depend on n).  extra_gy [33, N]: an upstream
         gradient of the net's outputs on the same samples -- its plain backward rides in the double backward's launch (round 6:
         one forward recomputation and one sweep for both); extra_dfeat: a data gradient to add instead (the two-launch form)"""
-        enc, dims = self.sdf.encoding, self.sdf.mlp_sdf.dims
+        enc, win = self.sdf.encoding, net.win
         gg = _enc_dbl_gather(enc, pts, win, g_n, dfeat)
-        dX2, _, _ = mlp_double_backward(dims, feat, ws, bs, e0, gg, into=(gb.dWs, gb.dbs), module=self.sdf.mlp_sdf, gy2_fm=extra_gy)
+        dX2, _, _ = mlp_double_backward(net.dims, feat, net.ws, net.bs, e0, gg, into=(net.gb.dWs, net.gb.dbs), module=self.sdf.mlp_sdf,
+                                        gy2_fm=extra_gy)
         if extra_dfeat is not None:
             dX2 = dX2 + extra_dfeat
         _enc_dbl_scatter(enc, pts, win, g_n, dfeat, dX2)
@@ -229,258 +263,241 @@ class ManualTrainer(Trainer):
     # ------------------------------------------------------------------ the background branch (NerfHash, models.py:431-526)
     def _bg_forward(self, bg, calib):
         """4-D lattice -> density + feature net -> [gelu(features), SH4(dir)] -> colour head -> (calibrated) sigmoid.  Everything
-        the compositing and the backward need, as a dict."""
+        the compositing and the backward need, as a record (net1, net2: `_net` of the two MLPs; rgbb_raw, ridx: None without calibration)."""
         bgn = self.bg
         self._params_ready(2)              # the background lattice's parameters (all-gather of the previous step, data parallel)
-        M = bg.samples_pos_4d.shape[0]
         p4, dirs_b = bg.samples_pos_4d, bg.samples_dirs
         feat4 = _enc_fwd(bgn.encoding, p4, bgn._win)
-        l1b = list(bgn.mlp_feat_and_density.layers)
-        w1b, b1b = [l.weight for l in l1b], [l.bias for l in l1b]
-        d1 = bgn.mlp_feat_and_density.dims
+        net1 = d1, _, w1b, b1b = _net(bgn.mlp_feat_and_density)
         fd = mlp_forward_wide_f16_raw(d1, feat4, w1b, b1b)                                # [65, M] on the fp16 matrix pipe (round 6)
         if fd is None:      # (the library declined: fp32 MFMAs)
             fd = mlp_forward_raw(d1, feat4, pack_params(d1, w1b, b1b))
         gel = torch.nn.functional.gelu(fd[1:65])
         sh4 = PermutoSDF.spherical_harmonics(dirs_b, 4)
         x2 = torch.cat([gel, sh4.t()], 0)                                                 # [80, M]
-        l2b = list(bgn.mlp_rgb.layers)
-        w2b, b2b = [l.weight for l in l2b], [l.bias for l in l2b]
-        d2 = bgn.mlp_rgb.dims
+        net2 = d2, _, w2b, b2b = _net(bgn.mlp_rgb)
         rgbb_fm = mlp_forward_raw(d2, x2, pack_params(d2, w2b, b2b))                      # [3, M]
-        B = dict(p4=p4, feat4=feat4, fd=fd, x2=x2, l1b=l1b, w1b=w1b, b1b=b1b, d1=d1, l2b=l2b, w2b=w2b, b2b=b2b, d2=d2)
-        if calib is not None:
-            cw, cb = calib
-            B["rgbb_raw"] = rgbb_fm.t().contiguous()                                      # [M, 3]
-            B["ridx"] = RaySamplesPacked.compute_per_sample_ray_idx(bg.ray_start_end_idx, M).long()
-            B["rgbb"] = torch.sigmoid(B["rgbb_raw"] * cw.index_select(0, B["ridx"]) + cb.index_select(0, B["ridx"]))
-        else:
-            B["rgbb"] = sigmoid_rows_raw(rgbb_fm)
-        B["raw_den"] = fd[0]                                                              # [M], a row of the feature-major output
-        return B
+        rgbb, rgbb_raw, ridx = _calib_sigmoid(calib, rgbb_fm, bg.ray_start_end_idx)
+        return SimpleNamespace(p4=p4, feat4=feat4, fd=fd, x2=x2, net1=net1, net2=net2, rgbb=rgbb, rgbb_raw=rgbb_raw, ridx=ridx,
+                               raw_den=fd[0])         # raw_den [M]: a row of the feature-major output
 
-    def _bg_backward(self, B, g_raw, g_rgbb, calib, R):
-        """-> (g_cw, g_cb) of the colour calibration (or None, None); the networks' gradients are set / accumulated"""
-        bgn = self.bg
-        g_cw = g_cb = None
-        rgbb = B["rgbb"]
-        if calib is not None:
-            cw, _ = calib
-            g_pre_b = g_rgbb * rgbb * (1.0 - rgbb)                                        # sigmoid
-            g_cb = torch.zeros(R, 3, device=self.dev).index_add_(0, B["ridx"], g_pre_b)
-            g_cw = torch.zeros(R, 3, device=self.dev).index_add_(0, B["ridx"], g_pre_b * B["rgbb_raw"])
-            g_pre_b_fm = (g_pre_b * cw.index_select(0, B["ridx"])).t().contiguous()
-        else:
-            g_pre_b_fm = sigmoid_rows_backward_raw(g_rgbb, rgbb)                          # [3, M], one launch
-        dX2b, dW2b, db2b = mlp_backward_raw(B["d2"], B["x2"], B["w2b"], B["b2b"], g_pre_b_fm, need_dx=True, into=B.get("into2"))
-        _set_grads(B["l2b"], dW2b, db2b)
-        g_fd = torch.cat([g_raw.view(1, -1), torch.ops.aten.gelu_backward(dX2b[:64], B["fd"][1:65])], 0)      # [65, M]
-        dX4, dW1b, db1b = mlp_backward_raw(B["d1"], B["feat4"], B["w1b"], B["b1b"], g_fd, need_dx=True, into=B.get("into1"))
-        _set_grads(B["l1b"], dW1b, db1b)
-        _enc_bwd(bgn.encoding, B["p4"], bgn._win, dX4)
+    def _bg_backward(self, B, g_raw, g_rgbb, calib, into1, into2):
+        """-> (g_cw, g_cb) of the colour calibration (or None, None); the networks' gradients are accumulated into the zero-filled
+        views into1 (density + feature net) / into2 (colour head) and set, the lattice's into its buffer"""
+        bgn, (d1, l1b, w1b, b1b), (d2, l2b, w2b, b2b) = self.bg, B.net1, B.net2
+        g_pre_b_fm, g_cw, g_cb = _calib_sigmoid_backward(calib, g_rgbb, B.rgbb, B.rgbb_raw, B.ridx)
+        dX2b, dW2b, db2b = mlp_backward_raw(d2, B.x2, w2b, b2b, g_pre_b_fm, need_dx=True, into=into2)
+        _set_grads(l2b, dW2b, db2b)
+        g_fd = torch.cat([g_raw.view(1, -1), torch.ops.aten.gelu_backward(dX2b[:64], B.fd[1:65])], 0)      # [65, M]
+        dX4, dW1b, db1b = mlp_backward_raw(d1, B.feat4, w1b, b1b, g_fd, need_dx=True, into=into1)
+        _set_grads(l1b, dW1b, db1b)
+        _enc_bwd(bgn.encoding, B.p4, bgn._win, dX4)
         return g_cw, g_cb
+
+    # ------------------------------------------------------------------ per-ray colour calibration (the sigmoids: _calib_sigmoid*)
+    def _calib_build(self, img_idx):
+        """per-ray calibration of both branches (models.py:384-385,523-524): colour = sigmoid(raw * cw + cb), [R, 3] each; cam [R]:
+        the ray's image, fixed [R, 1]: rays of the image that keeps the identity.  None without a calibration model."""
+        cc = self.colorcal
+        if cc is None:
+            return None
+        cam = img_idx.long()
+        fixed = (cam == cc.idx_with_fixed_calib)[:, None]
+        cw = torch.where(fixed, torch.ones_like(cc.weight_delta[:1]), 1.0 + cc.weight_delta.index_select(0, cam))
+        cb = torch.where(fixed, torch.zeros_like(cc.bias[:1]), cc.bias.index_select(0, cam))
+        return SimpleNamespace(cw=cw, cb=cb, fixed=fixed, cam=cam)
+
+    def _calib_assign_grads(self, calib, g_cw_bg, g_cb_bg, g_cw, g_cb):
+        """per-ray gradients of both branches (the foreground's None without foreground samples) -> weight_delta.grad, bias.grad"""
+        cc = self.colorcal
+        g_cw = g_cw_bg if g_cw is None else g_cw_bg + g_cw         # background first: the order the sums have always been taken in
+        g_cb = g_cb_bg if g_cb is None else g_cb_bg + g_cb
+        fixed3 = calib.fixed.expand(-1, 3)
+        gwd = torch.zeros_like(cc.weight_delta).index_add_(0, calib.cam, torch.where(fixed3, torch.zeros_like(g_cw), g_cw))
+        gbi = torch.zeros_like(cc.bias).index_add_(0, calib.cam, torch.where(fixed3, torch.zeros_like(g_cb), g_cb))
+        cc.weight_delta.grad, cc.bias.grad = gwd, gbi
+
+    # ------------------------------------------------------------------ the foreground branch: SDF net, colour net, NeuS compositing
+    def _fg_forward(self, st, fgs):
+        """-> (pred_fg [R, 3], bgT [R, 1]); st.fg: what the curvature term and the backward need (c_enc, c_sh: row offsets in
+        x_rgb = [colour encoding | SH | normal | geometry features]; rgb_raw, ridx: None without calibration)"""
+        net, rgbn = st.net, self.rgb
+        pts = fgs.samples_pos
+        feat = _enc_fwd(self.sdf.encoding, pts, net.win)
+        y = mlp_forward_raw(net.dims, feat, net.packed)                                   # [33, N]: sdf, geometry features
+        n, dfeat, e0 = self._sdf_gradient(feat, pts, net)
+        self._params_ready(1)              # the colour lattice's parameters: before the colour encode, not earlier
+        feat2 = _enc_fwd(rgbn.encoding, pts, rgbn._win)
+        sh = PermutoSDF.spherical_harmonics(fgs.samples_dirs, 5)
+        nn = _normalize3(n)
+        x_rgb = torch.cat([feat2, sh.t(), nn.t(), y[1:]], 0)                              # [111, N]
+        m = rgbn.mlp
+        wn = lipshitz_normalize_all_raw(m.weights_per_layer, m.lipshitz_bound_per_layer)      # all four layers, one launch
+        bsr = [b.detach() for b in m.biases_per_layer]
+        rgb_fm = mlp_forward_wide_f16_raw(m.dims, x_rgb, wn, bsr)                         # [3, N]
+        if rgb_fm is None:      # (the library declined: fp32 MFMAs)
+            rgb_fm = mlp_forward_raw(m.dims, x_rgb, pack_params(m.dims, wn, bsr))
+        rgb, rgb_raw, ridx = _calib_sigmoid(st.calib, rgb_fm, fgs.ray_start_end_idx)
+        st.fg = SimpleNamespace(samples=fgs, pts=pts, feat=feat, dfeat=dfeat, e0=e0, n=n, sdf_col=y[0].view(-1, 1), x_rgb=x_rgb,
+                                c_enc=feat2.shape[0], c_sh=feat2.shape[0] + sh.shape[1], wn=wn, bsr=bsr, rgb=rgb, rgb_raw=rgb_raw, ridx=ridx)
+        pred_fg, bgT, _ = neus_composite_forward_raw(fgs, st.fg.sdf_col, n, rgb, st.inv_s, st.cos_r)
+        return pred_fg, bgT
+
+    def _fg_backward(self, st):
+        """NeuS compositing -> colour net (+ Lipschitz normalisation) -> colour lattice; then everything that reached n and the
+        SDF net's outputs, through the SDF net once -> (g_cw, g_cb) of the colour calibration (or None, None)"""
+        fg, net, hp, rgbn, m = st.fg, st.net, self.hp, self.rgb, self.rgb.mlp
+        per_ray = hp.max_nr_samples_per_ray + 2 * hp.nr_samples_imp_sampling
+        g_sdf, g_nc, g_rgb, _ = neus_composite_backward_raw(fg.samples, per_ray, st.g_pred.contiguous(), st.g_bgT.contiguous(), fg.sdf_col,
+                                                            fg.n, fg.rgb, st.inv_s, st.cos_r, need_grad=True, need_rgb=True, need_inv_s=False)
+        g_pre_fm, g_cw, g_cb = _calib_sigmoid_backward(st.calib, g_rgb, fg.rgb, fg.rgb_raw, fg.ridx)
+        dXr, dWn, dbr = mlp_backward_raw(m.dims, fg.x_rgb, fg.wn, fg.bsr, g_pre_fm, need_dx=True, into=st.arena[2])
+        dws, dcs = lipshitz_normalize_all_backward_raw(m.weights_per_layer, m.lipshitz_bound_per_layer, dWn, dc_flat=st.arena[3])
+        for i, (w, c) in enumerate(zip(m.weights_per_layer, m.lipshitz_bound_per_layer)):
+            w.grad, c.grad, m.biases_per_layer[i].grad = dws[i], dcs[i].view_as(c), dbr[i]
+        _enc_bwd(rgbn.encoding, fg.pts, rgbn._win, dXr[:fg.c_enc])
+        self._dp_lattice_final(1)          # right after the colour encode backward: the colour lattice's gradient is final
+        g_n = st.g_n + g_nc + _normalize3(fg.n, dXr[fg.c_sh:fg.c_sh + 3].t().contiguous())
+        g_y = torch.cat([g_sdf.view(1, -1), dXr[fg.c_sh + 3:]], 0)                        # [33, N]
+        if st.curv is not None:
+            g_n = self._curvature_backward(st, g_n)
+        # first evaluation: from (sdf, geom) directly and from n through the double backward; ONE lattice scatter
+        if self.fuse_sdf_backward and double_backward_plus_supported(net.dims):
+            self._sdf_gradient_backward(g_n, fg.feat, fg.dfeat, fg.e0, fg.pts, net, extra_gy=g_y)
+        else:
+            dX1, _, _ = mlp_backward_raw(net.dims, fg.feat, net.ws, net.bs, g_y, need_dx=True, into=(net.gb.dWs, net.gb.dbs))
+            self._sdf_gradient_backward(g_n, fg.feat, fg.dfeat, fg.e0, fg.pts, net, extra_dfeat=dX1)
+        return g_cw, g_cb
+
+    # ------------------------------------------------------------------ curvature term: n against n at a point 1e-4 along a tangent
+    def _curvature_forward(self, st, weight):
+        """st.curv: the shifted points' evaluation; ga, gb2: the loss kernel's gradients w.r.t. n and the shifted points' normals"""
+        fg, net, n_fg = st.fg, st.net, st.n_fg
+        rnd = torch.randn_like(fg.pts)     # torch's first random draw of the step after the rays
+        shifted = torch.empty_like(fg.pts)
+        L.call("psdf_curvature_shift", L.c_l(n_fg), L.ptr(fg.pts), L.ptr(fg.n), L.ptr(rnd), L.c_f(1e-4), None, L.ptr(shifted), L.stream())
+        feat_s = _enc_fwd(self.sdf.encoding, shifted, net.win)
+        n2, dfeat_s, _ = self._sdf_gradient(feat_s, shifted, net)
+        ga, gb2 = torch.empty_like(fg.n), torch.empty_like(n2)
+        L.call("psdf_curvature_loss", L.c_l(n_fg), L.ptr(fg.n), L.ptr(n2), L.c_f(weight / n_fg), L.ptr(st.loss), L.ptr(ga), L.ptr(gb2),
+               L.stream())
+        st.curv = SimpleNamespace(rnd=rnd, shifted=shifted, feat_s=feat_s, dfeat_s=dfeat_s, ga=ga, gb2=gb2)
+
+    def _curvature_backward(self, st, g_n):
+        """-> g_n plus the term's two contributions: directly, and through the shifted points (which depend on n)"""
+        fg, net, cv = st.fg, st.net, st.curv
+        g_n = g_n + cv.ga
+        g_shift = self._sdf_gradient_backward(cv.gb2, cv.feat_s, cv.dfeat_s, fg.e0, cv.shifted, net, want_pos=True)
+        g_from_shift = torch.empty_like(fg.n)
+        L.call("psdf_curvature_shift", L.c_l(st.n_fg), None, L.ptr(fg.n), L.ptr(cv.rnd), L.c_f(1e-4), L.ptr(g_shift), L.ptr(g_from_shift),
+               L.stream())
+        return g_n + g_from_shift
+
+    # ------------------------------------------------------------------ off-surface term: 1024 points inside the sphere
+    def _offsurface_forward(self, st):
+        net = st.net
+        st.off = self.sphere.rand_points_inside(1024)      # torch's random draw after the curvature shift's
+        st.feat_o = _enc_fwd(self.sdf.encoding, st.off, net.win)
+        y_o = mlp_forward_raw(net.dims, st.feat_o, net.packed)
+        # the term's gradient w.r.t. the net's 33 outputs is zero except in row 0 (the SDF): a persistent [33, 1024] buffer whose
+        # rows 1.. stay zero, row 0 rewritten by the loss kernel every step (no fill, no copy)
+        if self._g_yo is None:
+            self._g_yo = torch.zeros((net.dims[-1], 1024), dtype=torch.float32, device=self.dev)
+        L.call("psdf_offsurface_loss", L.c_l(1024), L.ptr(y_o[0]), L.c_f(1e2), L.c_f(self.hp.offsurface_weight / 1024.0), L.ptr(st.loss),
+               L.ptr(self._g_yo[0]), L.stream())
+
+    def _offsurface_backward(self, st):
+        net = st.net
+        dXo, _, _ = mlp_backward_raw(net.dims, st.feat_o, net.ws, net.bs, self._g_yo, need_dx=True, into=(net.gb.dWs, net.gb.dbs))
+        _enc_bwd(self.sdf.encoding, st.off, net.win, dXo)
 
     # ------------------------------------------------------------------ one iteration of the main phase
     def _main_phase(self, reel, it, git, eikonal_weight):
-        """One stream by default.  PSDF_TRAIN_STREAMS=1 (round 4, measured and NOT kept as the default): the background branch is
-        independent of the SDF / colour branch between the samplers and the composition, and again between the composition's
-        backward and the optimiser, so its forward can run on a side stream beside the foreground forward, join for
-        `nerf_composite` (+ losses), and its backward beside the foreground backward.  On MI355X that LOST 9 %: 427 -> 389 it/s
-        at iteration 0, 400 -> 370 with every level open (profiles/r04_train_streams_ab.jsonl) -- the step is balanced between
-        host and device (~2.2 ms of launches against ~2.25 ms of kernels), and the stream switches and event records cost the
-        host more than the overlapped ~0.2 ms of small kernels give back.  (Cross-stream tensors live until this function
-        returns, after both streams have joined: the caching allocator's per-stream pools never hand a block to new work that
-        an unfinished kernel of the other stream still reads.)"""
+        """One stream.  (The background branch on a second stream was measured and lost 9 %: LABNOTES.md, "The background branch
+        on a second stream", profiles/r04_train_streams_ab.jsonl.)"""
         if not self._hand_written_step_applies():
             return Trainer._main_phase(self, reel, it, git, eikonal_weight)
-        hp, dev = self.hp, self.dev
-        cos_r = map_range_val(it, 0.0, hp.forced_variance_finish_iter, 0.0, 1.0)
+        st = self._main_forward(reel, it, git, eikonal_weight)
+        self._main_backward(st)
+        return st.loss.view(()), st.n_fg, st.R, True
+
+    def _step_rays(self, reel, git):
+        """-> (rays, the prefetched first half of their sampling or None)"""
+        if self._prefetch_valid(git, reel):
+            pf, self._prefetched = self._prefetched, None
+            torch.cuda.current_stream(self.dev).wait_event(pf["done"])
+            return pf["rays"], pf["begun"]
+        # (step() has seeded this iteration itself in that case: it asks the same question with the same reel)
+        self._drop_prefetch()
+        return self._draw_rays(reel), None
+
+    @torch.no_grad()
+    def _main_forward(self, reel, it, git, eikonal_weight):
+        """Sampling, every forward, every loss kernel (each produces its gradient in the same launch), grid refresh, prefetch.
+        The background branch's backward belongs to this half too: it needs nothing but the compositing's gradients, and enqueued
+        right behind them its lattice's reduction (data parallel) overlaps all the rest -- the background is finished when this
+        returns, `_main_backward` is the foreground's and the off-surface points'."""
+        hp, dev, sdfn = self.hp, self.dev, self.sdf
+        (o, d, gt, hit, img_idx, _), begun = self._step_rays(reel, git)
+        st = _Step(it=it, R=o.shape[0], calib=self._calib_build(img_idx),
+                   cos_r=map_range_val(it, 0.0, hp.forced_variance_finish_iter, 0.0, 1.0))
+        # the background network's forward is enqueued from the hook, while the host waits for the march's sample counts (it needs
+        # the background samples only), so the step's one host sync leaves no bubble on the GPU
+        fgs, bgs = self._samples(o, d, it, True, begun=begun, between=lambda bg_: setattr(st, "bg", self._bg_forward(bg_, st.calib)))
+        if st.bg is None:                  # (a sampler replaced from outside that left the hook alone)
+            st.bg = self._bg_forward(bgs, st.calib)
+        st.n_fg = fgs.samples_pos.shape[0]
+        self._params_ready(0)              # the SDF lattice's parameters, before anything below reads them (data parallel)
+        dims, _, ws, bs = _net(sdfn.mlp_sdf)
+        # the SDF network as the step's three evaluations share it; win: this iteration's lattice window, gb: its gradient buffer
+        st.net = SimpleNamespace(dims=dims, ws=ws, bs=bs, win=sdfn.window(it).contiguous(), packed=pack_params(dims, ws, bs),
+                                 gb=self.grad_buffers[0])
+        # exp(10 v) clipped, as RgbNet.neus_render computes it: evaluated in float32 on the host and uploaded (one 4-byte copy
+        # instead of a copy + exp + clamp on the device; the schedule is a host scalar anyway)
         forced_variance = map_range_val(it, 0.0, hp.forced_variance_finish_iter, 0.3, hp.forced_variance_finish)
-        main = torch.cuda.current_stream(dev)
-        side = self._side_stream() if self.overlap_streams else None
+        st.inv_s = torch.exp(torch.tensor(float(forced_variance) * 10.0, dtype=torch.float32, device="cpu")).clip(1e-6, 1e6).view(1).to(dev)
+        self.rgb.last_inv_s = st.inv_s.view(())
+        st.loss = L.zeroed_scalar(dev)     # ONE accumulator: every loss kernel of the step adds its (already weighted) term to it
+        self._pos_pool = None              # (zero-filled position gradients: a fresh pool per step)
+        st.arena = self._grad_arena()      # zero-filled parameter gradients of the nets without a persistent buffer: one fill
+        if st.n_fg:
+            pred_fg, bgT = self._fg_forward(st, fgs)
+        else:
+            pred_fg, bgT = torch.zeros(st.R, 3, device=dev), torch.ones(st.R, 1, device=dev)
+        # softplus -> opacity -> transmittance -> weights -> background radiance -> pred = pred_fg + bgT * pred_bg: one launch
+        _, pred = nerf_composite_forward_raw(bgs, st.bg.raw_den, st.bg.rgbb, pred_fg, bgT)
+        _, st.g_pred = l1_loss_raw(pred, gt, hit, loss=st.loss)
+        # pred = pred_fg + bgT * pred_bg and the whole background compositing backward, one launch
+        g_raw, g_rgbb, st.g_bgT = nerf_composite_backward_raw(bgs, hp.nr_samples_bg, st.g_pred, st.bg.raw_den, st.bg.rgbb, bgT)
+        st.g_cw_bg, st.g_cb_bg = self._bg_backward(st.bg, g_raw, g_rgbb, st.calib, st.arena[0], st.arena[1])
+        self._dp_lattice_final(2)          # right after the background backward: its lattice's reduction overlaps what follows
+        if st.n_fg:
+            _, st.g_n = eikonal_loss_raw(st.fg.n, scale=eikonal_weight / st.n_fg, loss=st.loss)
+            gw = map_range_val(it, hp.iter_start_reduce_curv, hp.iter_finish_reduce_curv, 1.0, 0.0)
+            if gw > 0.0:
+                self._curvature_forward(st, hp.curvature_weight * gw)
+        self._offsurface_forward(st)
+        # after the last loss kernel, before the first foreground backward launch: the refresh, THEN the next step's sampling
+        self._refresh_and_adapt(it, git, st.n_fg)
+        self._launch_prefetch(reel, git + 1)
+        return st
 
-        def fork(ev):
-            if side is not None:
-                ev.record(main)
-                side.wait_event(ev)
-
-        def join(ev):
-            if side is not None:
-                ev.record(side)
-                main.wait_event(ev)
-        side_ctx = (lambda: torch.cuda.stream(side)) if side is not None else contextlib.nullcontext
+    def _main_backward(self, st):
+        """The foreground's and the off-surface points' backward from what `_main_forward` left in `st` (the background's is under
+        way), the colour calibration's gradients of both branches, the Lipschitz bound's term (added to st.loss)."""
+        hp = self.hp
         with torch.no_grad():
-            begun = None
-            if self._prefetch_valid(git, reel):
-                pf, self._prefetched = self._prefetched, None
-                main.wait_event(pf["done"])
-                (o, d, gt, hit, img_idx, _), begun = pf["rays"], pf["begun"]
-            else:
-                # (step() has seeded this iteration itself in that case: it asks the same question with the same reel)
-                self._drop_prefetch()
-                o, d, gt, hit, img_idx, _ = self._draw_rays(reel)
-            R = o.shape[0]
-            cc = self.colorcal
-            calib = None
-            if cc is not None:              # per-ray calibration of both branches (models.py:384-385,523-524)
-                cam = img_idx.long()
-                fixed = (cam == cc.idx_with_fixed_calib)[:, None]
-                cw = torch.where(fixed, torch.ones_like(cc.weight_delta[:1]), 1.0 + cc.weight_delta.index_select(0, cam))
-                cb = torch.where(fixed, torch.zeros_like(cc.bias[:1]), cc.bias.index_select(0, cam))
-                calib = (cw, cb)
-            # one stream: the background network's forward is enqueued while the host waits for the march's sample counts (it
-            # needs the background samples only), so the step's one host sync leaves no bubble on the GPU
-            early_bg = {}
-            fg, bg = self._samples(o, d, it, True, begun=begun, between=None if side is not None else
-                                   (lambda bg_: early_bg.__setitem__("B", self._bg_forward(bg_, calib))))
-            n_fg = fg.samples_pos.shape[0]
-            self._params_ready(0)          # the SDF lattice's parameters (all-gather of the previous step, data parallel)
-            sdfn, rgbn = self.sdf, self.rgb
-            gb = self.grad_buffers[0]
-            lin = list(sdfn.mlp_sdf.layers)
-            ws, bs = [l.weight for l in lin], [l.bias for l in lin]
-            dims_s = sdfn.mlp_sdf.dims
-            win = sdfn.window(it).contiguous()
-            packed_s = pack_params(dims_s, ws, bs)
-            # exp(10 v) clipped, as RgbNet.neus_render computes it: evaluated in float32 on the host and uploaded (one 4-byte copy
-            # instead of a copy + exp + clamp on the device; the schedule is a host scalar anyway)
-            inv_s = torch.exp(torch.tensor(float(forced_variance) * 10.0, dtype=torch.float32, device="cpu")).clip(1e-6, 1e6).view(1).to(dev)
-            rgbn.last_inv_s = inv_s.view(())
-            loss = L.zeroed_scalar(dev)     # ONE accumulator: every loss kernel of the step adds its (already weighted) term to it
-            self._pos_pool = None           # (zero-filled position gradients: a fresh pool per step)
-            arena = self._grad_arena()      # zero-filled parameter gradients of the nets without a persistent buffer: one fill
-            # ================================================================= forward
-            if "B" in early_bg:
-                B = early_bg["B"]
-            else:
-                fork(self._events[0])
-                with side_ctx():
-                    B = self._bg_forward(bg, calib)
-            if n_fg:
-                pts, dirs = fg.samples_pos, fg.samples_dirs
-                feat = _enc_fwd(sdfn.encoding, pts, win)
-                y = mlp_forward_raw(dims_s, feat, packed_s)                                   # [33, N]: sdf, geometry features
-                n, dfeat, e0 = self._sdf_gradient(feat, pts, win, ws, bs)
-                # colour network
-                self._params_ready(1)
-                feat2 = _enc_fwd(rgbn.encoding, pts, rgbn._win)
-                sh = PermutoSDF.spherical_harmonics(dirs, 5)
-                nn = _normalize3(n)
-                x_rgb = torch.cat([feat2, sh.t(), nn.t(), y[1:]], 0)                         # [111, N]
-                c_enc, c_sh = feat2.shape[0], feat2.shape[0] + sh.shape[1]
-                m = rgbn.mlp
-                wn = lipshitz_normalize_all_raw(m.weights_per_layer, m.lipshitz_bound_per_layer)      # all four layers, one launch
-                bsr = [b.detach() for b in m.biases_per_layer]
-                rgb_fm = mlp_forward_wide_f16_raw(m.dims, x_rgb, wn, bsr)                                        # [3, N]
-                if rgb_fm is None:      # (the library declined: fp32 MFMAs)
-                    rgb_fm = mlp_forward_raw(m.dims, x_rgb, pack_params(m.dims, wn, bsr))
-                if cc is not None:
-                    rgb_raw = rgb_fm.t().contiguous()                                                            # [N, 3]
-                    ridx_fg = RaySamplesPacked.compute_per_sample_ray_idx(fg.ray_start_end_idx, n_fg).long()
-                    rgb = torch.sigmoid(rgb_raw * cw.index_select(0, ridx_fg) + cb.index_select(0, ridx_fg))
-                else:
-                    rgb = sigmoid_rows_raw(rgb_fm)
-                per_ray = hp.max_nr_samples_per_ray + 2 * hp.nr_samples_imp_sampling
-                sdf_col = y[0].view(-1, 1)
-                pred_fg, bgT, _ = neus_composite_forward_raw(fg, sdf_col, n, rgb, inv_s, cos_r)
-            else:
-                pred_fg = torch.zeros(R, 3, device=dev)
-                bgT = torch.ones(R, 1, device=dev)
-            join(self._events[1])
-            raw_den, rgbb = B["raw_den"], B["rgbb"]
-            # softplus -> opacity -> transmittance -> weights -> background radiance -> pred = pred_fg + bgT * pred_bg: one launch
-            _, pred = nerf_composite_forward_raw(bg, raw_den, rgbb, pred_fg, bgT)
-            # ---- losses (forward values; their gradients are produced by the same launches)
-            _, g_pred = l1_loss_raw(pred, gt, hit, loss=loss)
-            # pred = pred_fg + bgT * pred_bg and the whole background compositing backward, one launch; then the background
-            # networks' backward leaves for the side stream while this one goes on with the SDF losses
-            g_raw, g_rgbb, g_bgT = nerf_composite_backward_raw(bg, hp.nr_samples_bg, g_pred, raw_den, rgbb, bgT)
-            fork(self._events[2])
-            B["into1"], B["into2"] = arena[0], arena[1]
-            with side_ctx():
-                g_cw_bg, g_cb_bg = self._bg_backward(B, g_raw, g_rgbb, calib, R)
-            if side is None:
-                self._dp_lattice_final(2)      # the background lattice's gradient is final: its reduction overlaps what follows
-            g_n = None
-            curv = None
-            if n_fg:
-                _, g_n = eikonal_loss_raw(n, scale=eikonal_weight / n_fg, loss=loss)
-                gw = map_range_val(it, hp.iter_start_reduce_curv, hp.iter_finish_reduce_curv, 1.0, 0.0)
-                if gw > 0.0:
-                    rnd = torch.randn_like(pts)
-                    shifted = torch.empty_like(pts)
-                    L.call("psdf_curvature_shift", L.c_l(n_fg), L.ptr(pts), L.ptr(n), L.ptr(rnd), L.c_f(1e-4), None, L.ptr(shifted),
-                           L.stream())
-                    feat_s = _enc_fwd(sdfn.encoding, shifted, win)
-                    n2, dfeat_s, _ = self._sdf_gradient(feat_s, shifted, win, ws, bs)
-                    ga, gb2 = torch.empty_like(n), torch.empty_like(n2)
-                    L.call("psdf_curvature_loss", L.c_l(n_fg), L.ptr(n), L.ptr(n2), L.c_f(hp.curvature_weight * gw / n_fg), L.ptr(loss),
-                           L.ptr(ga), L.ptr(gb2), L.stream())
-                    curv = (rnd, shifted, feat_s, dfeat_s, ga, gb2)
-            off = self.sphere.rand_points_inside(1024)
-            feat_o = _enc_fwd(sdfn.encoding, off, win)
-            y_o = mlp_forward_raw(dims_s, feat_o, packed_s)
-            # the off-surface term's gradient w.r.t. the net's 33 outputs is zero except in row 0 (the SDF): a persistent
-            # [33, 1024] buffer whose rows 1.. stay zero, row 0 rewritten by the loss kernel every step (no fill, no copy)
-            if self._g_yo is None:
-                self._g_yo = torch.zeros((dims_s[-1], 1024), dtype=torch.float32, device=dev)
-            g_so = self._g_yo[0]
-            L.call("psdf_offsurface_loss", L.c_l(1024), L.ptr(y_o[0]), L.c_f(1e2), L.c_f(hp.offsurface_weight / 1024.0),
-                   L.ptr(loss), L.ptr(g_so), L.stream())
-            self._refresh_and_adapt(it, git, n_fg)
-            self._launch_prefetch(reel, git + 1)
-
-            # ================================================================= backward (foreground; the background's is under way)
             g_cw = g_cb = None
-            if n_fg:
-                g_sdf, g_nc, g_rgb, _ = neus_composite_backward_raw(fg, per_ray, g_pred.contiguous(), g_bgT.contiguous(), sdf_col, n,
-                                                                    rgb, inv_s, cos_r, need_grad=True, need_rgb=True, need_inv_s=False)
-                if cc is not None:
-                    g_pre = g_rgb * rgb * (1.0 - rgb)
-                    g_cb = torch.zeros(R, 3, device=dev).index_add_(0, ridx_fg, g_pre)
-                    g_cw = torch.zeros(R, 3, device=dev).index_add_(0, ridx_fg, g_pre * rgb_raw)
-                    g_pre_fm = (g_pre * cw.index_select(0, ridx_fg)).t().contiguous()
-                else:
-                    g_pre_fm = sigmoid_rows_backward_raw(g_rgb, rgb)
-                dXr, dWn, dbr = mlp_backward_raw(m.dims, x_rgb, wn, bsr, g_pre_fm, need_dx=True, into=arena[2])
-                dws, dcs = lipshitz_normalize_all_backward_raw(m.weights_per_layer, m.lipshitz_bound_per_layer, dWn, dc_flat=arena[3])
-                for i, (w, c) in enumerate(zip(m.weights_per_layer, m.lipshitz_bound_per_layer)):
-                    w.grad, c.grad, m.biases_per_layer[i].grad = dws[i], dcs[i].view_as(c), dbr[i]
-                _enc_bwd(rgbn.encoding, pts, rgbn._win, dXr[:c_enc])
-                self._dp_lattice_final(1)      # the colour lattice's gradient is final
-                g_n = g_n + g_nc + _normalize3(n, dXr[c_sh:c_sh + 3].t().contiguous())
-                g_y = torch.cat([g_sdf.view(1, -1), dXr[c_sh + 3:]], 0)                           # [33, N]
-                if curv is not None:
-                    rnd, shifted, feat_s, dfeat_s, ga, gb2 = curv
-                    g_n = g_n + ga
-                    g_shift = self._sdf_gradient_backward(gb2, feat_s, dfeat_s, e0, shifted, win, ws, bs, gb, want_pos=True)
-                    g_from_shift = torch.empty_like(n)
-                    L.call("psdf_curvature_shift", L.c_l(n_fg), None, L.ptr(n), L.ptr(rnd), L.c_f(1e-4), L.ptr(g_shift),
-                           L.ptr(g_from_shift), L.stream())
-                    g_n = g_n + g_from_shift
-                # first evaluation: from (sdf, geom) directly and from n through the double backward; ONE lattice scatter
-                if self.fuse_sdf_backward and double_backward_plus_supported(dims_s):
-                    self._sdf_gradient_backward(g_n, feat, dfeat, e0, pts, win, ws, bs, gb, extra_gy=g_y)
-                else:
-                    dX1, _, _ = mlp_backward_raw(dims_s, feat, ws, bs, g_y, need_dx=True, into=(gb.dWs, gb.dbs))
-                    self._sdf_gradient_backward(g_n, feat, dfeat, e0, pts, win, ws, bs, gb, extra_dfeat=dX1)
+            if st.fg is not None:
+                g_cw, g_cb = self._fg_backward(st)
             else:
                 self._dp_lattice_final(1)      # (no foreground samples on this rank: the same collective at the same point)
-            # ---- off-surface points
-            dXo, _, _ = mlp_backward_raw(dims_s, feat_o, ws, bs, self._g_yo, need_dx=True, into=(gb.dWs, gb.dbs))
-            _enc_bwd(sdfn.encoding, off, win, dXo)
-            join(self._events[3])
-            if cc is not None:
-                g_cw = g_cw_bg if g_cw is None else g_cw_bg + g_cw         # background first, as the single-stream order added them
-                g_cb = g_cb_bg if g_cb is None else g_cb_bg + g_cb
-                fixed3 = fixed.expand(-1, 3)
-                gwd = torch.zeros_like(cc.weight_delta).index_add_(0, cam, torch.where(fixed3, torch.zeros_like(g_cw), g_cw))
-                gbi = torch.zeros_like(cc.bias).index_add_(0, cam, torch.where(fixed3, torch.zeros_like(g_cb), g_cb))
-                cc.weight_delta.grad, cc.bias.grad = gwd, gbi
-        if it >= hp.iter_start_reduce_curv:      # the Lipschitz bound: four scalars, autograd is fine
-            lb = rgbn.mlp.lipshitz_bound_full().mean() * hp.lipshitz_weight
-            gs = torch.autograd.grad(lb, list(rgbn.mlp.lipshitz_bound_per_layer))
-            for c, g in zip(rgbn.mlp.lipshitz_bound_per_layer, gs):
+            self._offsurface_backward(st)
+            if st.calib is not None:
+                self._calib_assign_grads(st.calib, st.g_cw_bg, st.g_cb_bg, g_cw, g_cb)
+        if st.it >= hp.iter_start_reduce_curv:      # the Lipschitz bound: four scalars, autograd is fine
+            bounds = list(self.rgb.mlp.lipshitz_bound_per_layer)
+            lb = self.rgb.mlp.lipshitz_bound_full().mean() * hp.lipshitz_weight
+            for c, g in zip(bounds, torch.autograd.grad(lb, bounds)):
                 c.grad = g if c.grad is None else c.grad + g
-            loss = loss + lb.detach()
-        return loss.view(()), n_fg, R, True
+            st.loss = st.loss + lb.detach()
