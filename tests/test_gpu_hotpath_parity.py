@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import encode_float64 as e64
 from oracle import hotpath_oracle as ho
 from oracle import permuto_oracle as po
 
@@ -231,17 +232,11 @@ def test_cfg2_full_batch_dense_gradient_against_float64(dev, dy_kind, L_):
             idx = po.vertex_indices(rem0, rank, T_)
             bw = bary[:, :4].double()
             gl = x.grad[:, l * F_:(l + 1) * F_]
-            # float64 scatter WITHOUT atomics (a coarse level sends the whole chunk to a handful of rows: float64 atomics on one
-            # address serialise for seconds): sort by row, running sum, differences at the row boundaries
+            # float64 scatter WITHOUT atomics (oracle/encode_float64.scatter_rows: sort by row, every row's run summed by itself
+            # -- a coarse level sends the whole chunk to a handful of rows, where float64 atomics serialise)
             rows_all = idx.t().reshape(-1)                                             # [4 n]: vertex 0 of every sample, then 1, ...
             vals_all = torch.cat([gl * bw[:, r:r + 1] for r in range(4)], 0)           # [4 n, F]
-            order = torch.argsort(rows_all)
-            rs_, cs_ = rows_all[order], vals_all[order].cumsum(0)
-            uniq, counts = torch.unique_consecutive(rs_, return_counts=True)
-            ends = counts.cumsum(0) - 1
-            seg = cs_[ends]
-            seg[1:] = seg[1:] - cs_[ends[:-1]]
-            g64[l][uniq] += seg
+            g64[l] += e64.scatter_rows(rows_all, vals_all, T_)
             if c0 == 0:     # the rows / weights used for the float64 scatter are the kernel's: they reproduce its features
                 f_chk = sum(enc.lattice_values[l].detach().double().index_select(0, idx[:, r]) * bw[:, r:r + 1] for r in range(4))
                 e_rows = max(e_rows, float((f_chk - feat[l * F_:(l + 1) * F_, sl].t().double()).abs().max()))
