@@ -59,7 +59,12 @@ class _IntegrateCompat(torch.autograd.Function):
 
 def composite_equal(alpha, one_minus, rgb, nr_rays, per_ray, reference_compat=True):
     """transmittance T_i = prod_{j<i} one_minus_j, weights alpha*T, per-ray sum of w*rgb; [R*n, .] packed ray-major.
-    `reference_compat` selects the backward of the weighted sum: the reference kernel's (default) or the exact one."""
+    `reference_compat` selects the backward of the weighted sum: the reference kernel's (default) or the exact one.
+    DOMAIN OF VALIDITY of the BACKWARD: torch.cumprod is differentiated by autograd here, which divides by one_minus itself; the
+    reference's backward kernel (and ours) divides by clamp_min(one_minus, 1e-6) (VolumeRenderingGPU.cuh:1177,1184).  The two
+    agree while one_minus >= 1e-6 on every sample -- alpha <= 1 - 9e-7 -- i.e. NOT on a trained surface, where alpha == 1.0f on a
+    third of the samples of a crossing ray.  There oracle/composite_float64.py is the arbiter (it restates the kernels' formula;
+    tests/test_oracle_composite_float64.py shows the two differ by exactly the clamp factor on exactly the clamped samples)."""
     om = one_minus.view(nr_rays, per_ray)
     T = torch.cumprod(torch.cat([torch.ones(nr_rays, 1, dtype=om.dtype, device=om.device), om[:, :-1]], 1), dim=1)
     w = alpha.view(nr_rays, per_ray) * T

@@ -30,6 +30,13 @@ __device__ __forceinline__ Section section(float sdf, v3 dir, v3 grad, float dt,
   return s;
 }
 
+// torch.clip(q, 0, 1) of the opacity: a NaN stays a NaN (fminf / fmaxf return the bound instead, which turned a NaN sdf into
+// alpha = 0, a transparent sample).  For finite inputs with dt >= 0 no bound is ever active from below: ic <= 0 gives
+// en <= ep, so nc <= pc up to the monotonicity of expf, p >= -(a few ulp) and q = (p + 1e-5) / (pc + 1e-5) lies in (0, 1].
+// Hence the `gq = 0` arm of the backward kernels (q outside [0, 1]) is taken by a NaN q alone, where it changes nothing:
+// g_p = 0 / NaN is NaN all the same, as in torch's backward of clip followed by the division.
+__device__ __forceinline__ float clip01(float q) { return q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q); }
+
 struct RayIndex {
   const int* __restrict__ start_end;  // [R,2]
   int equal;                          // rays_have_equal_nr_of_samples

@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       const bool in = i < n;
       const int64_t m = s + (in ? i : n - 1);
       const Section sc = section(sdf[m], ld3(dirs + 3 * m), ld3(gradients + 3 * m), dt[m], inv_s, cos_anneal_ratio);
-      const float a = clampf(sc.q, 0.0f, 1.0f);
+      const float a = clip01(sc.q);
       const float om = (1.0f - a) + 1e-7f;
       const float fac = (i < n - 1) ? om : 1.f;
       const float incl = wave_incl_scan_mul(fac);
@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       a_[k] = T_[k] = gw_[k] = v_[k] = 0.f;
       if (64 * k < n) {     // wave-uniform
         const Section sc = section(sdf[m], ld3(dirs + 3 * m), ld3(gradients + 3 * m), dt[m], inv_s, rr);
-        const float a = clampf(sc.q, 0.0f, 1.0f);
+        const float a = clip01(sc.q);
         const float om = (1.0f - a) + 1e-7f;
         const float fac = (i < n - 1) ? om : 1.f;
         const float incl = wave_incl_scan_mul(fac);
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
         const v3 dir = ld3(dirs + 3 * m);
         const float d = dt[m];
         const Section sc = section(sdf[m], dir, ld3(gradients + 3 * m), d, inv_s, rr);
-        const float gq = (sc.q >= 0.0f && sc.q <= 1.0f) ? g_alpha : 0.0f;
+        const float gq = (sc.q >= 0.0f && sc.q <= 1.0f) ? g_alpha : 0.0f;    // 0 for a NaN q alone (clip01, composite_device.h)
         const float den = sc.c + 1e-5f;
         const float g_p = gq / den;
         const float g_c = -gq * (sc.p + 1e-5f) / (den * den);

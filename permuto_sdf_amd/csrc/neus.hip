@@ -23,7 +23,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   const float inv_s = inv_s_ptr[0];
   for (int64_t n = (int64_t)blockIdx.x * PSDF_BLOCK + threadIdx.x; n < N; n += (int64_t)gridDim.x * PSDF_BLOCK) {
     const Section s = section(sdf[n], ld3(dirs + 3 * n), ld3(gradients + 3 * n), dt[n], inv_s, cos_anneal_ratio);
-    const float a = clampf(s.q, 0.0f, 1.0f);
+    const float a = clip01(s.q);
     alpha[n] = a;
     if (one_minus_alpha) one_minus_alpha[n] = (1.0f - a) + 1e-7f;         // what cumprod_alpha2transmittance is fed
   }
@@ -41,7 +41,8 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     const v3 dir = ld3(dirs + 3 * n);
     const float d = dt[n];
     const Section s = section(sdf[n], dir, ld3(gradients + 3 * n), d, inv_s, r);
-    // clip(q, 0, 1) passes the gradient inside the closed interval (torch.clamp)
+    // clip(q, 0, 1) passes the gradient inside the closed interval (torch.clamp).  q lies in (0, 1] for finite inputs with
+    // dt >= 0 (clip01 in composite_device.h): the 0 arm is reached by a NaN q alone, and g_sdf is NaN there either way
     const float gq = (s.q >= 0.0f && s.q <= 1.0f) ? g_alpha[n] : 0.0f;
     const float den = s.c + 1e-5f;
     const float g_p = gq / den;

@@ -165,6 +165,9 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       const int idx = inverse ? (e - 1 - i) : (s + i);
       const float v = (i < n) ? vals[idx] : 0.f;
       const float incl = wave_incl_scan_add(v);
+      // exclusive (compute_cdf): formed as inclusive - v, so v is a term twice and the entry errs by u (prefix + |v|), not by u
+      // times itself as the reference's serial loop does (6e-8 absolute on a cdf in [0, 1]).  sdf_importance_cdf_kernel uses
+      // the same expression and is bit-identical to the operator chain through it: change both or neither.
       if (i < n) out[idx] = exclusive ? (carry + (incl - v)) : (carry + incl);
       carry = carry + __shfl(incl, 63, 64);
     }

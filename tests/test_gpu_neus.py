@@ -50,9 +50,50 @@ def test_neus_alpha_forward_backward_match_reference_expressions(dev, ratio, var
     magnitude = float(inv_vec.grad.abs().sum()) * chain
     assert abs(float(var_d.grad) - float(var.grad)) <= 2e-6 * magnitude + 1e-4 * abs(float(var.grad)), \
         (float(var_d.grad), float(var.grad), magnitude)
-    # interior of the clip: a share of the samples is clipped at 0 or 1 in this regime -- both branches are exercised
-    q = ((a_ref.detach() == 0) | (a_ref.detach() == 1)).float().mean()
-    assert 0.0 <= float(q) < 1.0
+    # the clip: from section(), ic <= 0, so en <= ep, nc <= pc (up to the monotonicity of the device expf) and
+    # q = (p + 1e-5) / (pc + 1e-5) lies in (0, 1]: over the case no alpha is 0, none exceeds 1, on the device and in the oracle.  The
+    # `gq = 0` arm of the backward (q outside [0, 1]) is therefore unreachable for finite inputs with dt >= 0; what it does for the
+    # one input that reaches it, a NaN, is pinned in test_neus_alpha_nan_sdf_propagates_like_torch_clip
+    for alpha in (a.detach().cpu(), a_ref.detach()):
+        assert float(alpha.min()) > 0.0 and float(alpha.max()) <= 1.0 and float((alpha == 1).float().mean()) < 1.0
+
+
+def test_neus_alpha_nan_sdf_propagates_like_torch_clip(dev):
+    """torch.clip keeps a NaN, and its backward hands the quotient a zero gradient that the division turns into NaN again: a NaN
+    sdf gives alpha = NaN, 1 - alpha + 1e-7 = NaN and g_sdf = NaN for that sample, on the CPU and on the device, in the opacity
+    kernels and in the fused ones -- and touches no other sample.  (fminf / fmaxf in the kernels' clip used to return alpha = 0: a
+    transparent sample in place of the NaN.)"""
+    from permuto_sdf import RaySamplesPacked
+    from permuto_sdf_amd.neus import (neus_alpha_backward_raw, neus_alpha_forward_raw, neus_composite_backward_raw,
+                                      neus_composite_forward_raw)
+    N, bad = 192, 70
+    sdf, dirs, grad, dt = _inputs(N, 3, scale=0.01)
+    sdf[bad] = float("nan")
+    inv_s = torch.tensor([300.0])
+    sdf_r = sdf.clone().requires_grad_(True)
+    a_ref, om_ref = no.neus_alpha(sdf_r, dirs, grad, dt, inv_s, 0.6)
+    a_ref.sum().backward()
+    others = torch.ones(N, dtype=torch.bool)
+    others[bad] = False
+    assert torch.isnan(a_ref[bad]).all() and torch.isnan(om_ref[bad]).all() and torch.isnan(sdf_r.grad[bad]).all()      # torch, CPU
+    assert torch.isfinite(a_ref[others]).all() and torch.isfinite(sdf_r.grad[others]).all()
+    d = lambda t: t.to(dev)
+    a, om = neus_alpha_forward_raw(d(sdf), d(dirs), d(grad), d(dt), d(inv_s), 0.6)
+    g_sdf, g_grad, _ = neus_alpha_backward_raw(torch.ones(N, 1, device=dev), d(sdf), d(dirs), d(grad), d(dt), d(inv_s), 0.6)
+    assert torch.isnan(a[bad]).all() and torch.isnan(om[bad]).all() and torch.isnan(g_sdf[bad]).all()
+    assert torch.isfinite(a[others]).all() and torch.isfinite(g_sdf[others]).all() and torch.isfinite(g_grad[others]).all()
+    assert (a.cpu()[others] - a_ref.detach()[others]).abs().max() <= 2e-6
+    # fused: three rays of 64 samples, the NaN in the second one
+    rs = RaySamplesPacked(3, N, device=dev)
+    rs.rays_have_equal_nr_of_samples, rs.fixed_nr_of_samples_per_ray = True, 64
+    rs.samples_dirs, rs.samples_dt = d(dirs), d(dt)
+    rs.cur_nr_samples.fill_(N)
+    rgb = torch.rand(N, 3, device=dev)
+    pred, bg, w = neus_composite_forward_raw(rs, d(sdf), d(grad), rgb, d(inv_s), 0.6, want_weights=True)
+    assert torch.isnan(pred[1]).all() and torch.isnan(w[bad]).all() and torch.isfinite(pred[[0, 2]]).all() and torch.isfinite(bg[[0, 2]]).all()
+    gs, gg, gr, gi = neus_composite_backward_raw(rs, 64, torch.ones(3, 3, device=dev), torch.ones(3, 1, device=dev), d(sdf), d(grad), rgb,
+                                                 d(inv_s), 0.6, need_inv_s=False)
+    assert torch.isnan(gs[bad]).all() and torch.isfinite(gs[:64]).all() and torch.isfinite(gs[128:]).all()
 
 
 def test_neus_alpha_edge_cases(dev):
