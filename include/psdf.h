@@ -537,6 +537,43 @@ int psdf_combine_uniform_samples_with_imp(int nr_rays, const int* uni_start_end,
     imp_sdf, int out_max_nr_samples, float* out_pos, float* out_dirs, float* out_z, float* out_dt, float* out_sdf,
     float* out_fixed_dt, int* out_start_end, int* out_cur_nr_samples, int* scratch, void* stream);
 
+/* ---- mesh.hip ---- */
+/* replaces: the host side of extract_mesh_from_sdf_model (permuto_sdf_py/utils/sdf_utils.py:252-292: the n^3 volume assembled in
+   host memory, then skimage.measure.marching_cubes) by marching tetrahedra on the device, streamed over slabs of x-planes.  The
+   triangulation, the inside test (vol - level < 0 in fp32), the welding by grid edge and the vertex order are those of
+   compat/skimage/measure.py; the tables and the winding rule are csrc/mesh_tables.h.
+   Layout shared by the three passes: the volume is [X, Y, Z] fp32 with Z fastest; the per-point buffers vol / valid / mask / vincl
+   hold `nplanes` consecutive x-planes starting at global plane `xbase` (xbase + nplanes <= X).  `valid` (bytes, NULL = all): points
+   that carry a value; an edge needs two valid ends, a cell eight valid corners, other values are never read.
+   psdf_mesh_classify: vertex planes [p0, p1) -> mask (7 bits: owned crossing edges in the directions z, y, yz, x, xz, xy, xyz;
+   written at the buffer's slots) and vcount [(p1 - p0) Y Z] int32 = popcount(mask); value planes p0 .. min(p1, X - 1) must be in the
+   buffer.  Cell planes [c0, c1), c1 <= X - 1 -> tcount [(c1 - c0) Y Z] int32 triangles per cell (indexed like points; 0 on the
+   last row / column); value planes c0 .. c1 must be in the buffer.  Either range may be empty.
+   The caller scans both counts INCLUSIVELY (no scan here: nothing allocates) and stores, at the buffer's slots, vincl = scan of
+   vcount + number of vertices of earlier slabs; tincl = scan of tcount stays local to the range. */
+int psdf_mesh_classify(const float* vol, const uint8_t* valid, float level, int X, int Y, int Z, int xbase, int nplanes, int p0,
+    int p1, int c0, int c1, uint8_t* mask, int32_t* vcount, int32_t* tcount, void* stream);
+/* vertices of the edges owned by planes [p0, p1), at row (global id - v_off) of verts [., 3] (index coordinates, fp32:
+   t = f_lo / (f_lo - f_hi), p = p_lo + (p_hi - p_lo) t), edges [., 2] int64 (optional: linear indices (x Y + y) Z + z of the two
+   ends, lo first) and normals [., 3] (optional; -2 unless the buffer holds the whole volume: the stand-in's normal, np.gradient of
+   the volume at both ends interpolated with t, normalised, negated) */
+int psdf_mesh_emit_vertices(const float* vol, float level, int X, int Y, int Z, int xbase, int nplanes, int p0, int p1, const
+    uint8_t* mask, const int32_t* vincl, int64_t v_off, float* verts, int64_t* edges, float* normals, void* stream);
+/* triangles of cell planes [c0, c1) as global vertex ids, at rows tincl - count of faces [., 3] int32, ordered by (cell,
+   tetrahedron, triangle); mask / vincl of vertex planes c0 .. c1 must be in the buffer */
+int psdf_mesh_emit_faces(const float* vol, const uint8_t* valid, float level, int X, int Y, int Z, int xbase, int nplanes, int c0,
+    int c1, const uint8_t* mask, const int32_t* vincl, const int32_t* tincl, int32_t* faces, void* stream);
+/* replaces: the torch.meshgrid + chunk loop of sdf_utils.py:262-276.  points [count, 3] of the linear indices first .. first +
+   count - 1 (relative to plane x0, Z fastest) of the grid with axis coordinates xs [nx], ys [Y], zs [Z] (the caller's
+   torch.linspace, bit for bit) */
+int psdf_mesh_grid_points(int nx, int Y, int Z, int x0, int64_t first, int64_t count, const float* xs, const float* ys, const
+    float* zs, float* points, void* stream);
+/* sparse extraction: valid[i] = 1 iff one of the 27 probes points[i] + {-h, 0, h}^3 lies in an occupied voxel of the Morton-ordered
+   occupancy grid (h = mesh spacing <= voxel size: then every corner of a cell that contains a surface point of an occupied voxel is
+   valid); skip[i] = !valid[i] (optional: the mask the masked encode / MLP launches take) */
+int psdf_mesh_sparse_mask(int64_t count, int nr_voxels_per_dim, float extent, const float* grid_translation, const uint8_t*
+    grid_occupancy, const float* points, float h, uint8_t* valid, uint8_t* skip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
