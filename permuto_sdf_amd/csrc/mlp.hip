@@ -217,14 +217,11 @@ __global__ void __launch_bounds__(PSDF_BLOCK, 2)
 // The same evaluator on the bf16 matrix pipe with split fp32 operands (mlp_device.h, "split-bf16 operand path").
 // CH: k-steps of layer 0 whose loads are issued together (= all of them when the input has <= 64 features).
 // activation of the split forwards: packed arithmetic for the two-piece fp16 form (VALU-count bound), one element per
-// instruction for the three-piece bf16 form (see apply_gelu_scalar / apply_gelu_packed in mlp_device.h)
-#if !defined(PSDF_FWD_F16_GELU_PACKED)
-#define PSDF_FWD_F16_GELU_PACKED 1
-#endif
-#define GELU_SPLIT(T_, H_)                                           \
-  do {                                                               \
-    if constexpr (F16 && PSDF_FWD_F16_GELU_PACKED) apply_gelu_packed<T_>(H_); \
-    else apply_gelu_scalar<T_>(H_);                                  \
+// instruction for the three-piece bf16 form (see gelu_rational / gelu_rational2 in gelu_device.h)
+#define GELU_SPLIT(T_, H_)                        \
+  do {                                            \
+    if constexpr (F16) apply_gelu_packed<T_>(H_); \
+    else apply_gelu_scalar<T_>(H_);               \
   } while (0)
 template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16 = false>
 __global__ void __launch_bounds__(PSDF_BLOCK, 2)

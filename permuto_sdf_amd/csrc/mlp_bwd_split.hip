@@ -4,7 +4,7 @@
 // VALU work do not overlap on gfx950 (profiles/r01_mfma_valu_overlap.txt), and the fp32 kernel (mlp_bwd.hip) spends 49 %
 // of its time in them.  Structure (attic/prototypes/mlp_bwd_split_bf16_v3.hip is the standalone prototype with its history):
 //   * 16-sample tiles on v_mfma_f32_16x16x32_bf16, one wave per SIMD, dW accumulators persistent in registers (176);
-//   * forward recomputed from X; gelu and gelu' from one exponential and one reciprocal (gelu_rational below);
+//   * forward recomputed from X; gelu and gelu' from one exponential and one reciprocal (gelu_rational_both, gelu_device.h);
 //   * the sample<->feature transposes that the dW products need are MFMAs against a 0/1 operand (no LDS, no VALU);
 //   * a dW MFMA (K = samples, only 16 of 32 slots filled by a tile) carries two piece products in its two K halves
 //     (480 instead of 612 MFMAs per tile);
@@ -17,102 +17,18 @@
 // profiles/r02_mlp_bwd_prototype_timings.txt); gradients within 1e-6 relative of a float64 evaluation.  Built with
 // -mllvm -amdgpu-mfma-vgpr-form=1 (only the accumulators live in AGPRs); the K0 <= 36 instantiation in its own translation
 // unit (mlp_bwd_split_double.hip).
-#include "psdf_common.h"
-#include "mlp_dispatch.h"
+#include "mlp_split_layout.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using IMG = SplitImage<3>;   // three bf16 pieces per operand: [tile][k-step 2][piece 3][lane 64]
+constexpr uint32_t ONE_BF16 = 0x3F80u;
 
-constexpr int HID = 64, NT = 4 /* 16-feature tiles of a hidden layer */;   // NT0 (template) = tiles covering the input: 3 (<= 48) or 4 (<= 64)
-__host__ __device__ inline int kf(int s, int g, int j) { return 32 * s + 16 * (j >> 2) + 4 * g + (j & 3); }
-
-// ------------------------------------------------------------------ LDS image (units: 16-byte lane records)
-// every layer: [tile][k-step 2][piece 3][lane 64]
-constexpr int RECL = NT * 2 * 3 * 64;
-constexpr int OFF_W0 = 0, OFF_W1 = RECL, OFF_W2 = 2 * RECL, OFF_T2 = 3 * RECL, OFF_T1 = 4 * RECL, OFF_T0 = 5 * RECL;
-constexpr int off_f32(int nt0) { return 5 * RECL + nt0 * 2 * 3 * 64; }
-constexpr int TAIL_FLOATS = 3 * HID + HID + 1;  // biases of the three hidden layers, final weights, final bias
-constexpr int NWAVES = 4;
-constexpr size_t img_aligned(int nt0) { return ((size_t)off_f32(nt0) * 16 + TAIL_FLOATS * 4 + 15) / 16 * 16; }
-// gradient image (floats): dW1 [64][64 (K0 used)], dW2 [64][64], dW3 [64][64], db1, db2, db3 [64], dW4 [64], db4
-constexpr int G_W1 = 0, G_W2 = 4096, G_W3 = 8192, G_B1 = 12288, G_B2 = 12352, G_B3 = 12416, G_W4 = 12480, G_B4 = 12544,
-              G_TOTAL = 12545;
-
-__device__ __forceinline__ float erf_fast(float a) {
-  const float t = fabsf(a), s = a * a;
-  float r = fmaf(-1.72853470e-5f, t, 3.83197126e-4f);
-  float u = fmaf(-3.88396438e-3f, t, 2.42546219e-2f);
-  r = fmaf(r, s, u);
-  r = fmaf(r, t, -1.06777877e-1f);
-  r = fmaf(r, t, -6.34846687e-1f);
-  r = fmaf(r, t, -1.28717512e-1f);
-  r = fmaf(r, t, -t);
-  const float hi = copysignf(1.0f - __expf(r), a);
-  float q = -5.96761703e-4f;
-  q = fmaf(q, s, 4.99119423e-3f);
-  q = fmaf(q, s, -2.67681349e-2f);
-  q = fmaf(q, s, 1.12819925e-1f);
-  q = fmaf(q, s, -3.76125336e-1f);
-  q = fmaf(q, s, 1.28379166e-1f);
-  const float lo = fmaf(q, a, a);
-  return t > 0.927734375f ? hi : lo;
-}
-// gelu and its derivative Phi(z) + z phi(z) from one erf and one exp
-// Three interchangeable evaluators; the kernel picks per instantiation (see gelu_both below).
-// tools/gelu_fit_rational.py: gelu AND gelu' from ONE exponential and ONE reciprocal (the recompute needs both):
-//   E = exp(-z^2/2), t = 1/(1 + p|z|), Phi(-|z|) = t P6(t) E, cdf = z < 0 ? Phi(-|z|) : 1 - Phi(-|z|),
-//   gelu = z cdf, gelu' = cdf + z E / sqrt(2 pi).  17 instructions against ~30; error against float64: gelu 1.8e-7 |z|
-//   (the fp32 formula 0.5 z (1 + erf(z / sqrt 2)) itself: 1.1e-7 |z|), gelu' 1.9e-7.
-__device__ __forceinline__ void gelu_rational(float z, float& hval, float& gprime) {
-  const float E = __builtin_amdgcn_exp2f(z * z * -0.72134752044448170368f);
-  const float t = __builtin_amdgcn_rcpf(fmaf(fabsf(z), 0.39f, 1.0f));
-  float q = 5.384693295e-02f;
-  q = fmaf(q, t, -2.582434118e-01f);
-  q = fmaf(q, t, 3.751679361e-01f);
-  q = fmaf(q, t, -1.663514599e-02f);
-  q = fmaf(q, t, 1.944366544e-01f);
-  q = fmaf(q, t, 1.514270604e-01f);
-  const float tail = q * t * E;
-  const float cdf = z < 0.f ? tail : 1.0f - tail;
-  hval = z * cdf;
-  gprime = fmaf(z, E * 0.3989422804014327f, cdf);
-}
-// torch's formula 0.5 z (1 + erf(z / sqrt 2)): one erf (itself one exp) and one more exp
-__device__ __forceinline__ void gelu_erf(float z, float& hval, float& gprime) {
-  const float cdf = fmaf(0.5f, erf_fast(z * 0.70710678118654752440f), 0.5f);
-  const float pdf = 0.3989422804014327f * __expf(-0.5f * z * z);
-  hval = z * cdf;
-  gprime = fmaf(z, pdf, cdf);
-}
-// tools/gelu_fit.py: e = Phi(-t) = exp2(P8(t)), t = min(|z|, 5.75); gelu = max(z, 0) - t e (error 8.6e-8 |z| against float64, the
-// fp32 erf formula itself has 1.06e-7 |z|); gelu' = (z < 0 ? e : 1 - e) + z phi(t) from the same e (1.5e-7)
-__device__ __forceinline__ void gelu_poly(float z, float& hval, float& gprime) {
-  const float t = fminf(fabsf(z), 5.75f);
-  float p = -2.772052994e-06f;
-  p = fmaf(p, t, 3.862077210e-05f);
-  p = fmaf(p, t, -1.825476502e-04f);
-  p = fmaf(p, t, -1.458701736e-04f);
-  p = fmaf(p, t, 7.075471804e-03f);
-  p = fmaf(p, t, -5.250502750e-02f);
-  p = fmaf(p, t, -4.592049122e-01f);
-  p = fmaf(p, t, -1.151105762e+00f);
-  p = fmaf(p, t, -1.000000000e+00f);
-  const float e = __builtin_amdgcn_exp2f(p);
-  hval = fmaf(-t, e, fmaxf(z, 0.f));
-  const float cdf = z < 0.f ? e : 1.0f - e;
-  const float pdf = 0.3989422804014327f * __builtin_amdgcn_exp2f(t * t * -0.72134752044448170368f);
-  gprime = fmaf(copysignf(t, z), pdf, cdf);
-}
-// Measured on the headline batch (profiles/r02_mlp_bwd_prototype_timings.txt): rational 1.37 ms, erf 1.47 ms, poly 1.47 ms
-// for the double-staged instantiation (zero scratch in all three).  The widest instantiation (K0 > 48) is at the register
-// limit and the rational form's extra live values spill there (44 B scratch; a spill reload waits for the LDS-DMA in
-// flight), so it keeps erf.
+// gelu and gelu' of the recompute: the one-exponential rational fit where the registers allow it, the erf form in the widest
+// instantiation (measurements and the spill that decides it: gelu_rational_both in gelu_device.h)
 template <bool RATIONAL>
 __device__ __forceinline__ void gelu_both(float z, float& hval, float& gprime) {
-  if constexpr (RATIONAL) gelu_rational(z, hval, gprime);
+  if constexpr (RATIONAL) gelu_rational_both(z, hval, gprime);
   else gelu_erf(z, hval, gprime);
 }
 
@@ -126,7 +42,6 @@ __device__ __forceinline__ uint32_t top_pair(float hi, float lo) {  // {top half
 }
 // eight fp32 -> three bf16x8 pieces by truncation of the running remainder.  The remainders are formed on PAIRS
 // (v_pk_add_f32: one issue slot for two subtractions -- with one wave per SIMD a packed instruction costs what a plain one does)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 trunc_pair(f32x2 v) {
   return f32x2{__uint_as_float(__float_as_uint(v.x) & 0xFFFF0000u), __uint_as_float(__float_as_uint(v.y) & 0xFFFF0000u)};
 }
@@ -155,10 +70,6 @@ struct AT {  // dZ side
 struct BT {  // H side
   bf16x8 t20, t01;
 };
-__device__ __forceinline__ bf16x8 halves(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) {
-  const u32x4 q = {a0, a1, b0, b1};
-  return __builtin_bit_cast(bf16x8, q);
-}
 // four fp32 (a feature-lane tile: samples 4 g + r) -> H-side operands
 __device__ __forceinline__ void split4(const f32x4& t, BT& o) {
   const f32x2 va = {t[0], t[1]}, vb = {t[2], t[3]};
@@ -167,8 +78,8 @@ __device__ __forceinline__ void split4(const f32x4& t, BT& o) {
   const uint32_t p0a = top_pair(va.y, va.x), p0b = top_pair(vb.y, vb.x);
   const uint32_t p1a = top_pair(r1a.y, r1a.x), p1b = top_pair(r1b.y, r1b.x);
   const uint32_t p2a = top_pair(r2a.y, r2a.x), p2b = top_pair(r2b.y, r2b.x);
-  o.t20 = halves(p2a, p2b, p0a, p0b);
-  o.t01 = halves(p0a, p0b, p1a, p1b);
+  o.t20 = halves<bf16x8>(p2a, p2b, p0a, p0b);
+  o.t01 = halves<bf16x8>(p0a, p0b, p1a, p1b);
 }
 
 // out[t] += W(tile t, k-step s) x operand pieces: six products, smallest first; two tiles at a time so that consecutive
@@ -190,28 +101,6 @@ __device__ __forceinline__ void mac16(f32x4 (&out)[NTILE], const BP& b, const u3
 #undef PROD
   }
 }
-// B operand of k-step s from the D tiles 2s, 2s+1 of an activation
-__device__ __forceinline__ void step_operand(const f32x4 (&act)[NT], int s, float (&x)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    x[j] = act[2 * s][j];
-    x[4 + j] = act[2 * s + 1][j];
-  }
-}
-// 0/1 operand that selects the 16 features of tile 2s+u out of a k-step (the same for every s)
-__device__ __forceinline__ bf16x8 ident_op(int u, int lane) {
-  const int c = lane & 15, g = lane >> 4;
-  u32x4 q;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int j0 = 2 * i, j1 = 2 * i + 1;
-    const uint32_t lo = ((j0 >> 2) == u && 4 * g + (j0 & 3) == c) ? 0x3F80u : 0u;
-    const uint32_t hi = ((j1 >> 2) == u && 4 * g + (j1 & 3) == c) ? 0x3F80u : 0u;
-    q[i] = lo | (hi << 16);
-  }
-  return __builtin_bit_cast(bf16x8, q);
-}
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 // fp32 feature-lane tile (exact: the three pieces sum to the value): register r of lane (f, g) = feature f, sample 4 g + r
 __device__ __forceinline__ f32x4 transpose_f32(const BP& b, bf16x8 id) {
   f32x4 o = zero4();
@@ -230,25 +119,15 @@ __device__ __forceinline__ void transpose_pieces(const BP& b, bf16x8 id, AT& out
     q[p][0] = top_pair(o[1], o[0]);
     q[p][1] = top_pair(o[3], o[2]);
   }
-  out.t02 = halves(q[0][0], q[0][1], q[2][0], q[2][1]);
-  out.t11 = halves(q[1][0], q[1][1], q[1][0], q[1][1]);
-  out.t00 = halves(q[0][0], q[0][1], q[0][0], q[0][1]);
+  out.t02 = halves<bf16x8>(q[0][0], q[0][1], q[2][0], q[2][1]);
+  out.t11 = halves<bf16x8>(q[1][0], q[1][1], q[1][0], q[1][1]);
+  out.t00 = halves<bf16x8>(q[0][0], q[0][1], q[0][0], q[0][1]);
 }
 __device__ __forceinline__ f32x4 dw_mac(f32x4 acc, const AT& A, const BT& B) {
   acc = MFMA16(A.t02, B.t20, acc);   // smallest first
   acc = MFMA16(A.t11, B.t01, acc);
   acc = MFMA16(A.t00, B.t01, acc);
   return acc;
-}
-template <int NTILE>
-__device__ __forceinline__ void bias_init(f32x4 (&acc)[NTILE], const float* __restrict__ b, int g) {
-#pragma unroll
-  for (int t = 0; t < NTILE; t++) acc[t] = *reinterpret_cast<const f32x4*>(b + 16 * t + 4 * g);
-}
-template <int NTILE>
-__device__ __forceinline__ void zero_init(f32x4 (&acc)[NTILE]) {
-#pragma unroll
-  for (int t = 0; t < NTILE; t++) acc[t] = zero4();
 }
 // in place: acc <- gelu(acc), gp <- gelu'(acc)
 template <bool RATIONAL>
@@ -278,7 +157,6 @@ __device__ __forceinline__ void chain(const f32x4 (&in)[NT], f32x4 (&out)[NTILE]
     per_step(s, b);
   }
 }
-// backward of one layer: dH chain (hands the pieces of dZ to the transposes), then dW[to][ti] += dZ(to) x H(ti)
 // backward of one layer: dH chain (hands the pieces of dZ to the transposes), then dW[to][ti] += dZ(to) x H(ti)
 template <int NTO, int NTI>
 __device__ __forceinline__ void layer_bwd(const f32x4 (&dz)[NT], f32x4 (&dh)[NTO], const u32x4* __restrict__ wT, int lane,
@@ -311,14 +189,14 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
   // this one behind themselves for the batches that leave their range (mlp_bwd_split_f16.hip, "range guard")
   if (only_if && only_if[0] == 0u) return;
   extern __shared__ __align__(16) u32x4 lds[];
-  constexpr size_t IMG_ALIGNED = img_aligned(NT0);
-  constexpr int OFF_F32 = off_f32(NT0);
+  constexpr size_t IMG_ALIGNED = IMG::aligned(NT0);
+  constexpr int OFF_F32 = IMG::off_f32(NT0);
   constexpr int NREC = (int)(IMG_ALIGNED / 16);
   for (int i = threadIdx.x; i < NREC; i += NWAVES * 64) lds[i] = img[i];
   __syncthreads();
   const float* tail = reinterpret_cast<const float*>(lds + OFF_F32);
   const int lane_k = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bf16x8 id[2] = {ident_op(0, lane_k), ident_op(1, lane_k)};
+  const bf16x8 id[2] = {ident_op<bf16x8, ONE_BF16>(0, lane_k), ident_op<bf16x8, ONE_BF16>(1, lane_k)};
   f32x4 dW1[NT][NT0], dW2[NT][NT], dW3[NT][NT];
 #pragma unroll
   for (int to = 0; to < NT; to++) {
@@ -392,7 +270,7 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
       for (int s = 0; s < 2; s++) {
         BP bx;
         split8(xs[s], bx);
-        mac16<NT>(a, bx, lds + OFF_W0 + s * 192 + lane);
+        mac16<NT>(a, bx, lds + IMG::OFF_W0 + s * 192 + lane);
       }
     }
     // single staging buffer: take the two dY operands now and refill the buffer for the next tile at once
@@ -407,13 +285,13 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
     }
     act_both<NT0 == 3>(a, g1);  // a = h1
     bias_init<NT>(b, tail + HID, g);
-    chain<NT>(a, b, lds + OFF_W1, lane, [&](int s, const BP& p) {
+    chain<NT>(a, b, lds + IMG::OFF_W1, lane, [&](int s, const BP& p) {
       h1T[2 * s] = transpose_f32(p, id[0]);
       h1T[2 * s + 1] = transpose_f32(p, id[1]);
     });
     act_both<NT0 == 3>(b, g2);  // b = h2
     bias_init<NT>(a, tail + 2 * HID, g);
-    chain<NT>(b, a, lds + OFF_W2, lane, [&](int s, const BP& p) {
+    chain<NT>(b, a, lds + IMG::OFF_W2, lane, [&](int s, const BP& p) {
       h2T[2 * s] = transpose_f32(p, id[0]);
       h2T[2 * s + 1] = transpose_f32(p, id[1]);
     });
@@ -449,14 +327,14 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
     }
     // ---------------- layer 3
     zero_init<NT>(a);
-    layer_bwd<NT, NT>(dz, a, lds + OFF_T2, lane, id, h2T, dW3, db3);  // a = dH2^T
+    layer_bwd<NT, NT>(dz, a, lds + IMG::OFF_T2, lane, id, h2T, dW3, db3);  // a = dH2^T
 #pragma unroll
     for (int t = 0; t < NT; t++) a[t] *= g2[t];                       // dZ2^T
     // ---------------- layer 2 (the prefetch goes out here: late enough that the early part of the tile does not wait on
     // it, early enough for an HBM round trip before the next tile)
     if (DOUBLE && tile + tstride < ntiles) prefetch(tile + tstride, stage + (cur ^ 1) * stage_floats);
     zero_init<NT>(dz);
-    layer_bwd<NT, NT>(a, dz, lds + OFF_T1, lane, id, h1T, dW2, db2);  // dz = dH1^T
+    layer_bwd<NT, NT>(a, dz, lds + IMG::OFF_T1, lane, id, h1T, dW2, db2);  // dz = dH1^T
 #pragma unroll
     for (int t = 0; t < NT; t++) dz[t] *= g1[t];                      // dZ1^T
     // ---------------- layer 1: H = X in feature-lane order, straight from the staged rows
@@ -479,7 +357,7 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
       }
     }
     zero_init<NT0>(dx);
-    layer_bwd<NT0, NT0>(dz, dx, lds + OFF_T0, lane, id, xT, dW1, db1);  // dx = dX^T
+    layer_bwd<NT0, NT0>(dz, dx, lds + IMG::OFF_T0, lane, id, xT, dW1, db1);  // dx = dX^T
     if (dX) {
 #pragma unroll
       for (int t = 0; t < NT0; t++)
@@ -547,7 +425,7 @@ __global__ void mlp_split_reduce_kernel(const float* __restrict__ partial, int n
   if (e >= G_TOTAL) return;
   float s = 0.f;
   for (int b = blockIdx.y; b < nimg; b += gridDim.y) s += partial[(size_t)b * G_TOTAL + e];
-  if (e < G_W2) {
+  if (e < G_W2) {   // (the same ladder as in the sibling file: mlp_split_layout.h says why it is not a shared function)
     const int o = e >> 6, k = e & 63;
     if (k < K0) atomicAdd(&dW0[o * K0 + k], s);
   } else if (e < G_W3) {
@@ -594,20 +472,11 @@ __global__ void mlp_split_pack_kernel(int K0, const float* __restrict__ W0, cons
     const int q = t - im * PER_IMG;
     const int lane = q & 63, s = (q >> 6) & 1, tile = q >> 7;
     const int c = lane & 15, g = lane >> 4, row = 16 * tile + c;
-    const int off[6] = {OFF_W0, OFF_W1, OFF_W2, OFF_T2, OFF_T1, OFF_T0};
+    const int off[6] = {IMG::OFF_W0, IMG::OFF_W1, IMG::OFF_W2, IMG::OFF_T2, IMG::OFF_T1, IMG::OFF_T0};
     uint16_t out[3][8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      const int k0 = 32 * s + 8 * g + j, kc = kf(s, g, j);
-      float w;
-      switch (im) {
-        case 0: w = k0 < K0 ? W0[row * K0 + k0] : 0.f; break;
-        case 1: w = W1[row * HID + kc]; break;
-        case 2: w = W2[row * HID + kc]; break;
-        case 3: w = W2[kc * HID + row]; break;                 // transposed images: row is an INPUT neuron of the layer
-        case 4: w = W1[kc * HID + row]; break;
-        default: w = row < K0 ? W0[kc * K0 + row] : 0.f; break;
-      }
+      const float w = image_weight(im, row, s, g, j, K0, W0, W1, W2);
       uint16_t p[3];
       split3(w, p);
       out[0][j] = p[0]; out[1][j] = p[1]; out[2][j] = p[2];
@@ -620,8 +489,8 @@ __global__ void mlp_split_pack_kernel(int K0, const float* __restrict__ W0, cons
     }
   } else {
     const int e = t - NTHR;
-    float* tail = reinterpret_cast<float*>(rec + (size_t)off_f32(NT0) * 8);
-    if (e < HID) tail[e] = b0[e];
+    float* tail = reinterpret_cast<float*>(rec + (size_t)IMG::off_f32(NT0) * 8);
+    if (e < HID) tail[e] = b0[e];   // (the same ladder as in the sibling file, see mlp_split_layout.h)
     else if (e < 2 * HID) tail[e] = b1[e - HID];
     else if (e < 3 * HID) tail[e] = b2[e - 2 * HID];
     else if (e < 4 * HID) tail[e] = W3[e - 3 * HID];
@@ -671,29 +540,22 @@ int psdf_mlp_backward_split(int n_layers, const int* dims, int64_t N, const floa
 
 }  // extern "C"
 
-static int64_t split_blocks(int64_t N) {
-  const int64_t ntiles = (N + 15) / 16;
-  int64_t blocks = (ntiles + NWAVES - 1) / NWAVES;
-  return blocks > 256 ? 256 : blocks;  // one workgroup per CU; each wave walks many tiles
-}
 size_t psdf::mlp_backward_split_scratch_bytes(int K0, int64_t N) {
-  return img_aligned(K0 <= 48 ? 3 : 4) + (size_t)split_blocks(N) * G_TOTAL * sizeof(float);
+  return IMG::aligned(K0 <= 48 ? 3 : 4) + (size_t)split_blocks(N) * G_TOTAL * sizeof(float);
 }
 int psdf::mlp_backward_split_impl(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
                                   const float* const* biases, const float* dY, float* dX, float* const* dW, float* const* db,
                                   hipStream_t st, char* scratch, const uint32_t* only_if) {
-  if (!dims || !dW || !db || !baseline_split_shape(n_layers, dims, 64, 1)) return PSDF_ERR_UNSUPPORTED;
+  const int rc0 = split_check(n_layers, dims, 52 /* what fits 160 KB of LDS, see lds_bytes */, N, X, weights, biases, dY, dW, db);
+  if (rc0 != PSDF_OK) return rc0;
   const int K0 = dims[0];
   const int rows4 = (K0 + 3) & ~3;
   const int nt0 = K0 <= 48 ? 3 : 4;
   const size_t stage_bytes = (size_t)NWAVES * (rows4 * 16 + 64) * 4;
-  const bool dbl = nt0 == 3 && img_aligned(3) + 2 * stage_bytes <= 160 * 1024;      // K0 <= 36
-  const size_t img_bytes = img_aligned(nt0);
+  const bool dbl = nt0 == 3 && IMG::aligned(3) + 2 * stage_bytes <= 160 * 1024;      // K0 <= 36
+  const size_t img_bytes = IMG::aligned(nt0);
   const size_t lds_bytes = img_bytes + (dbl ? 2 : 1) * stage_bytes;
   if (lds_bytes > 160 * 1024) return PSDF_ERR_UNSUPPORTED;
-  if (N <= 0 || !X || !weights || !biases || !dY) return PSDF_ERR_ARG;
-  for (int l = 0; l < 4; l++)
-    if (!weights[l] || !biases[l] || !dW[l] || !db[l]) return PSDF_ERR_ARG;
   const int64_t blocks = split_blocks(N);
   const size_t part_bytes = (size_t)blocks * G_TOTAL * sizeof(float);
   if (!scratch) scratch = (char*)psdf::stream_scratch(img_bytes + part_bytes, st);   // NULL while capturing

@@ -36,48 +36,26 @@
 // region: slower), other scheduler strategies (max-ilp, iterative-*: more spills or longer).
 // Accuracy against float64: tests/test_gpu_mlp.py::test_split_f16_backward_matches_float64.  Built with
 // -mllvm -amdgpu-mfma-vgpr-form=1 -fno-slp-vectorize (build.py).
-#include "psdf_common.h"
-#include "mlp_dispatch.h"
+#include "mlp_split_layout.h"
 #include <stdio.h>
 #include <type_traits>
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int HID = 64, NT = 4 /* 16-feature tiles of a hidden layer */;   // NT0 (template) = tiles covering the input: 3 (<= 48) or 4 (<= 64)
-__host__ __device__ inline int kf(int s, int g, int j) { return 32 * s + 16 * (j >> 2) + 4 * g + (j & 3); }
-
-// ------------------------------------------------------------------ LDS image (units: 16-byte lane records)
-// every layer: [tile][k-step 2][piece 2][lane 64]
 constexpr int NP = 2;   // pieces per operand
-constexpr int RECL = NT * 2 * NP * 64;
-constexpr int OFF_W0 = 0, OFF_W1 = RECL, OFF_W2 = 2 * RECL, OFF_T2 = 3 * RECL, OFF_T1 = 4 * RECL, OFF_T0 = 5 * RECL;
-constexpr int off_f32(int nt0) { return 5 * RECL + nt0 * 2 * NP * 64; }
-constexpr int TAIL_FLOATS = 3 * HID + HID + 1;  // biases of the three hidden layers, final weights, final bias
-constexpr int NWAVES = 4;
-constexpr size_t img_aligned(int nt0) { return ((size_t)off_f32(nt0) * 16 + TAIL_FLOATS * 4 + 15) / 16 * 16; }
-// gradient image (floats): dW1 [64][64 (K0 used)], dW2 [64][64], dW3 [64][64], db1, db2, db3 [64], dW4 [64], db4
-constexpr int G_W1 = 0, G_W2 = 4096, G_W3 = 8192, G_B1 = 12288, G_B2 = 12352, G_B3 = 12416, G_W4 = 12480, G_B4 = 12544,
-              G_TOTAL = 12545;
+using IMG = SplitImage<NP>;   // [tile][k-step 2][piece 2][lane 64]
+constexpr uint32_t ONE_F16 = 0x3C00u;
 
-// gelu AND gelu' = Phi(z) + z phi(z) from ONE exponential and ONE reciprocal (tools/gelu_fit_rational.py; the recompute needs
-// both):  E = exp(-z^2/2), t = 1/(1 + p|z|), Phi(-|z|) = t P6(t) E, cdf = z < 0 ? Phi(-|z|) : 1 - Phi(-|z|),
-//   gelu = z cdf, gelu' = cdf + z E / sqrt(2 pi).  Error against float64: gelu 1.8e-7 |z| (the fp32 formula
-//   0.5 z (1 + erf(z / sqrt 2)) itself: 1.1e-7 |z|), gelu' 1.9e-7.  (An erf-based and a pure-polynomial evaluator were measured
-//   beside it in round 2 -- 1.47 ms against 1.37 ms, profiles/r02_mlp_bwd_prototype_timings.txt -- and are gone.)
-// Written for TWO PAIRS at a time in packed fp32 arithmetic: gelu_rational4 below.  (The forward kernels evaluate the same
-// fit as max(z, 0) - |z| Phi(-|z|), mlp_device.h: equal up to the last bit or two of an fp32 evaluation.)
+// gelu and gelu' of the recompute: gelu_rational4 (gelu_device.h), the one-exponential rational fit on two packed pairs.  (An
+// erf-based and a pure-polynomial evaluator were measured beside it in round 2 -- 1.47 ms against 1.37 ms,
+// profiles/r02_mlp_bwd_prototype_timings.txt.)
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 
 struct BP {  // the two fp16 pieces of one 8-element operand: p[0] = high, p[1] = low
   f16x8 p[NP];
 };
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // two fp32 -> {high pieces, low pieces}, each a packed pair (element 0 in the low half).  The high piece is fp16(x) rounded to
 // NEAREST (v_cvt_pk_f16_f32, new on gfx950; rounds 3-5 truncated with v_cvt_pkrtz): |x - high| <= 2^-11 of x's binade and a
 // multiple of its fp32 ulp, so the remainder is exact in fp32 and has at most 12 significant bits; the low piece keeps 11 of
@@ -92,12 +70,13 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // hazard recogniser must see the VALU write -- an MFMA that reads a register needs two wait states after a VALU wrote it (the
 // compiler puts an s_nop 1 there), and a build with the instruction in an asm statement computed garbage whenever the
 // scheduler happened to place one directly in front of an MFMA.
+// (One of three two-piece splits kept apart on purpose: wsplit2 in mlp_wide.hip is the subtract-and-convert form on a pair,
+// split8h in mlp_device.h the same on eight values; same pieces, different instructions.)
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
-  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
   float one = 1.0f;
   asm("" : "+s"(one));
-  const h2_t h2 = __builtin_convertvector(f32x2{x0, x1}, h2_t);   // v_cvt_pk_f16_f32 (round to nearest even)
-  h2_t l;
+  const h2v_t h2 = __builtin_convertvector(f32x2{x0, x1}, h2v_t);   // v_cvt_pk_f16_f32 (round to nearest even)
+  h2v_t l;
   l[0] = (_Float16)__builtin_fmaf(x0, one, -(float)h2[0]);
   l[1] = (_Float16)__builtin_fmaf(x1, one, -(float)h2[1]);
   hi = __builtin_bit_cast(uint32_t, h2);
@@ -126,41 +105,15 @@ struct AT {  // dZ side
 struct BT {  // H side
   f16x8 t00, t11;
 };
-__device__ __forceinline__ f16x8 halves(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) {
-  const u32x4 q = {a0, a1, b0, b1};
-  return __builtin_bit_cast(f16x8, q);
-}
 // four fp32 (a feature-lane tile: samples 4 g + r) -> H-side operand
 __device__ __forceinline__ void split4(const f32x4& t, BT& o) {
   uint32_t ha, la, hb, lb;
   split2(t[0], t[1], ha, la);
   split2(t[2], t[3], hb, lb);
-  o.t00 = halves(ha, hb, ha, hb);
-  o.t11 = halves(la, lb, la, lb);
+  o.t00 = halves<f16x8>(ha, hb, ha, hb);
+  o.t11 = halves<f16x8>(la, lb, la, lb);
 }
 
-// B operand of k-step s from the D tiles 2s, 2s+1 of an activation
-__device__ __forceinline__ void step_operand(const f32x4 (&act)[NT], int s, float (&x)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    x[j] = act[2 * s][j];
-    x[4 + j] = act[2 * s + 1][j];
-  }
-}
-// 0/1 operand that selects the 16 features of tile 2s+u out of a k-step (the same for every s)
-__device__ __forceinline__ f16x8 ident_op(int u, int lane) {
-  const int c = lane & 15, g = lane >> 4;
-  u32x4 q;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int j0 = 2 * i, j1 = 2 * i + 1;
-    const uint32_t lo = ((j0 >> 2) == u && 4 * g + (j0 & 3) == c) ? 0x3C00u : 0u;
-    const uint32_t hi = ((j1 >> 2) == u && 4 * g + (j1 & 3) == c) ? 0x3C00u : 0u;
-    q[i] = lo | (hi << 16);
-  }
-  return __builtin_bit_cast(f16x8, q);
-}
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 // fp32 feature-lane tile (the two pieces sum exactly in fp32): register r of lane (f, g) = feature f, sample 4 g + r
 __device__ __forceinline__ f32x4 transpose_f32(const BP& b, f16x8 id) {
   f32x4 o = zero4();
@@ -168,8 +121,6 @@ __device__ __forceinline__ f32x4 transpose_f32(const BP& b, f16x8 id) {
   o = MFMA16(b.p[0], id, o);
   return o;
 }
-__device__ __forceinline__ f32x2 pk_fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x2 sp2(float v) { return f32x2{v, v}; }
 __device__ __forceinline__ f32x2 lo2(const f32x4& v) { return __builtin_shufflevector(v, v, 0, 1); }
 __device__ __forceinline__ f32x2 hi2(const f32x4& v) { return __builtin_shufflevector(v, v, 2, 3); }
 // elementwise products of register quadruples as TWO packed multiplies (the file is built without the SLP vectoriser, which is
@@ -187,8 +138,8 @@ template <> struct Sum<true> {
   f32x2 v;
   __device__ __forceinline__ void clear() { v = f32x2{0.f, 0.f}; }
   __device__ __forceinline__ void add(const f32x4& o, const f32x4& w) {
-    v = pk_fma2(lo2(o), lo2(w), v);
-    v = pk_fma2(hi2(o), hi2(w), v);
+    v = pk_fma(lo2(o), lo2(w), v);
+    v = pk_fma(hi2(o), hi2(w), v);
   }
   __device__ __forceinline__ float total() const { return v.x + v.y; }
 };
@@ -210,7 +161,7 @@ __device__ __forceinline__ void transpose_pieces(const BP& b, f16x8 id, AT& out,
     q[p][0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(o[0], o[1]));
     q[p][1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(o[2], o[3]));
   }
-  out.t01 = halves(q[0][0], q[0][1], q[1][0], q[1][1]);
+  out.t01 = halves<f16x8>(q[0][0], q[0][1], q[1][0], q[1][1]);
 }
 // The 176 dW accumulators live in ACCUMULATION registers for the whole kernel: the empty asm statements pin the value to an
 // AGPR on either side of its MFMA pair, and the compiler then emits the AGPR form of the two MFMAs itself (and keeps them in
@@ -227,68 +178,13 @@ __device__ __forceinline__ f32x4 dw_mac(f32x4 acc, const AT& A, const BT& B) {
 }
 // (PIN = false: the wave-pair kernel below.  A kernel whose budget is 256 registers gets 128 + 128 as soon as anything in it asks
 // for an accumulation register; without such a request the whole budget is VGPRs and the MFMAs use their VGPR form throughout.)
-template <int NTILE>
-__device__ __forceinline__ void bias_init(f32x4 (&acc)[NTILE], const float* __restrict__ b, int g) {
-#pragma unroll
-  for (int t = 0; t < NTILE; t++) acc[t] = *reinterpret_cast<const f32x4*>(b + 16 * t + 4 * g);
-}
-template <int NTILE>
-__device__ __forceinline__ void zero_init(f32x4 (&acc)[NTILE]) {
-#pragma unroll
-  for (int t = 0; t < NTILE; t++) acc[t] = zero4();
-}
-// two PAIRS at once, statement by statement: a dependent v_pk_fma_f32 needs a wait state after the one that feeds it, and the
-// Horner chain of a single pair is nothing but such dependences (117 s_nop per tile) -- two chains side by side fill them
-__device__ __forceinline__ void gelu_rational4(f32x2 za, f32x2 zb, f32x2& ha, f32x2& hb, f32x2& ga, f32x2& gb) {
-  const f32x2 ea = (za * za) * sp2(-0.72134752044448170368f), eb = (zb * zb) * sp2(-0.72134752044448170368f);
-  const f32x2 Ea = {__builtin_amdgcn_exp2f(ea.x), __builtin_amdgcn_exp2f(ea.y)};
-  const f32x2 Eb = {__builtin_amdgcn_exp2f(eb.x), __builtin_amdgcn_exp2f(eb.y)};
-#if !defined(PSDF_F16_GELU_ABS_MOD)
-#define PSDF_F16_GELU_ABS_MOD 1
-#endif
-#if PSDF_F16_GELU_ABS_MOD
-  // 1 + p |z|: two scalar fmas whose |.| is a source modifier (no instruction), instead of two v_and + one packed fma -- the
-  // results only feed v_rcp_f32, which is scalar anyway; same fused arithmetic, bit-identical
-  const f32x2 da = {__builtin_fmaf(__builtin_fabsf(za.x), 0.39f, 1.0f), __builtin_fmaf(__builtin_fabsf(za.y), 0.39f, 1.0f)};
-  const f32x2 db = {__builtin_fmaf(__builtin_fabsf(zb.x), 0.39f, 1.0f), __builtin_fmaf(__builtin_fabsf(zb.y), 0.39f, 1.0f)};
-#else
-  const f32x2 da = pk_fma2(f32x2{fabsf(za.x), fabsf(za.y)}, sp2(0.39f), sp2(1.0f));
-  const f32x2 db = pk_fma2(f32x2{fabsf(zb.x), fabsf(zb.y)}, sp2(0.39f), sp2(1.0f));
-#endif
-  const f32x2 ta = {__builtin_amdgcn_rcpf(da.x), __builtin_amdgcn_rcpf(da.y)};
-  const f32x2 tb = {__builtin_amdgcn_rcpf(db.x), __builtin_amdgcn_rcpf(db.y)};
-  f32x2 qa = sp2(5.384693295e-02f), qb = sp2(5.384693295e-02f);
-#define HORNER(C) qa = pk_fma2(qa, ta, sp2(C)); qb = pk_fma2(qb, tb, sp2(C));
-  HORNER(-2.582434118e-01f) HORNER(3.751679361e-01f) HORNER(-1.663514599e-02f) HORNER(1.944366544e-01f) HORNER(1.514270604e-01f)
-#undef HORNER
-  const f32x2 la = (qa * ta) * Ea, lb = (qb * tb) * Eb;
-#if !defined(PSDF_F16_GELU_COPYSIGN)
-#define PSDF_F16_GELU_COPYSIGN 1
-#endif
-#if PSDF_F16_GELU_COPYSIGN
-  // cdf = 1/2 + sign(z) (1/2 - Phi(-|z|)): one v_bfi_b32 per value instead of a compare and a select (1/2 - l >= 0 always);
-  // differs from `z < 0 ? l : 1 - l` by at most one rounding of the sum (6e-8)
-  const f32x2 ma = sp2(0.5f) - la, mb = sp2(0.5f) - lb;
-  const f32x2 ca = f32x2{__builtin_copysignf(ma.x, za.x), __builtin_copysignf(ma.y, za.y)} + sp2(0.5f);
-  const f32x2 cb = f32x2{__builtin_copysignf(mb.x, zb.x), __builtin_copysignf(mb.y, zb.y)} + sp2(0.5f);
-#else
-  const f32x2 oa = sp2(1.0f) - la, ob = sp2(1.0f) - lb;
-  const f32x2 ca = {za.x < 0.f ? la.x : oa.x, za.y < 0.f ? la.y : oa.y};
-  const f32x2 cb = {zb.x < 0.f ? lb.x : ob.x, zb.y < 0.f ? lb.y : ob.y};
-#endif
-  ha = za * ca;
-  hb = zb * cb;
-  ga = pk_fma2(za, Ea * sp2(0.3989422804014327f), ca);
-  gb = pk_fma2(zb, Eb * sp2(0.3989422804014327f), cb);
-}
 // in place: acc <- gelu(acc), gp <- gelu'(acc)
 __device__ __forceinline__ void act_both(f32x4 (&acc)[NT], f32x4 (&gp)[NT]) {
 #pragma unroll
   for (int t = 0; t < NT; t++) {
-    f32x2 ha, hb, ga, gb;
-    gelu_rational4(f32x2{acc[t][0], acc[t][1]}, f32x2{acc[t][2], acc[t][3]}, ha, hb, ga, gb);
-    acc[t] = f32x4{ha.x, ha.y, hb.x, hb.y};
-    gp[t] = f32x4{ga.x, ga.y, gb.x, gb.y};
+    f32x4 h;
+    gelu_rational4(acc[t], h, gp[t]);
+    acc[t] = h;
   }
 }
 // chain layer over the two k-steps of `in`; per_step(s, pieces) sees the operand pieces of each k-step.
@@ -441,8 +337,8 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
   uint32_t out_of_range = 0u;   // range guard: some lane of this wave met |input| or |hidden activation| >= RANGE_LIMIT (uniform)
   float sc, isc;
   const int kscale = dy_scale(absmax[0], sc, isc);      // 2^kscale * max|dY| in [2^4, 2^5)
-  constexpr size_t IMG_ALIGNED = img_aligned(NT0);
-  constexpr int OFF_F32 = off_f32(NT0);
+  constexpr size_t IMG_ALIGNED = IMG::aligned(NT0);
+  constexpr int OFF_F32 = IMG::off_f32(NT0);
   constexpr int NREC = (int)(IMG_ALIGNED / 16);
   for (int i = threadIdx.x; i < NREC; i += NWAVES * 64) lds[i] = img[i];
   __syncthreads();
@@ -450,7 +346,7 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
   // (the wave index as a scalar: tile numbers, loop bounds and the prefetch condition are then uniform to the compiler -- the
   //  prefetch block was exec-masked with vector compares before)
   const int lane_k = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const f16x8 id[2] = {ident_op(0, lane_k), ident_op(1, lane_k)};
+  const f16x8 id[2] = {ident_op<f16x8, ONE_F16>(0, lane_k), ident_op<f16x8, ONE_F16>(1, lane_k)};
   f32x4 dW1[NT][NT0], dW2[NT][NT], dW3[NT][NT];
 #pragma unroll
   for (int to = 0; to < NT; to++) {
@@ -531,7 +427,7 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
     bias_init<NT>(a, tail, g);
     {
       f16x8 w00[NT][NP], w01[NT][NP];
-      load_w<NT>(w00, lds + OFF_W0 + lane);
+      load_w<NT>(w00, lds + IMG::OFF_W0 + lane);
       float xs[2][8];
 #pragma unroll
       for (int s = 0; s < 2; s++)
@@ -543,7 +439,7 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
       __builtin_amdgcn_sched_barrier(0);
       BP bx;
       split8(xs[0], bx);
-      load_w<NT>(w01, lds + OFF_W0 + (NP * 64) + lane);
+      load_w<NT>(w01, lds + IMG::OFF_W0 + (NP * 64) + lane);
       __builtin_amdgcn_sched_barrier(0);
       mac16r<NT>(a, bx, w00);
       split8(xs[1], bx);
@@ -558,7 +454,7 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
 #pragma unroll
       for (int t = 0; t < NT; t++) gl[t * 64] = g1[t];
     }
-    chain<NT>(a, b, lds + OFF_W1, lane, [&](int s, const BP& p) {
+    chain<NT>(a, b, lds + IMG::OFF_W1, lane, [&](int s, const BP& p) {
       h1T[2 * s] = transpose_f32(p, id[0]);
       h1T[2 * s + 1] = transpose_f32(p, id[1]);
     });
@@ -570,7 +466,7 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
 #pragma unroll
       for (int t = 0; t < NT; t++) gl[(NT + t) * 64] = g2[t];
     }
-    chain<NT>(b, a, lds + OFF_W2, lane, [&](int s, const BP& p) {
+    chain<NT>(b, a, lds + IMG::OFF_W2, lane, [&](int s, const BP& p) {
       h2T[2 * s] = transpose_f32(p, id[0]);
       h2T[2 * s + 1] = transpose_f32(p, id[1]);
     });
@@ -625,14 +521,14 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
     for (int t = 0; t < NT; t++) dz[t] = mul4(dz[t], mul4s(w4[t], dy));
     // ---------------- layer 3
     zero_init<NT>(a);
-    layer_bwd<NT, NT, PAIR>(dz, a, lds + OFF_T2, lane, id, h2T, dW3, db3, rT);  // a = dH2^T
+    layer_bwd<NT, NT, PAIR>(dz, a, lds + IMG::OFF_T2, lane, id, h2T, dW3, db3, rT);  // a = dH2^T
 #pragma unroll
     for (int t = 0; t < NT; t++) a[t] = mul4(a[t], GLDS ? gl[(NT + t) * 64] : g2[t]);   // dZ2^T
     // ---------------- layer 2 (the prefetch goes out here: late enough that the early part of the tile does not wait on
     // it, early enough for an HBM round trip before the next tile)
     if (tile + tstride < ntiles) prefetch(tile + tstride, stage + (cur ^ 1) * stage_floats);
     zero_init<NT>(dz);
-    layer_bwd<NT, NT, PAIR>(a, dz, lds + OFF_T1, lane, id, h1T, dW2, db2, rT);  // dz = dH1^T
+    layer_bwd<NT, NT, PAIR>(a, dz, lds + IMG::OFF_T1, lane, id, h1T, dW2, db2, rT);  // dz = dH1^T
 #pragma unroll
     for (int t = 0; t < NT; t++) dz[t] = mul4(dz[t], GLDS ? gl[t * 64] : g1[t]);         // dZ1^T
     // ---------------- layer 1: H = X in feature-lane order, straight from the staged rows
@@ -643,7 +539,7 @@ __global__ void __launch_bounds__(NWAVES * 64, 1)
       xT[u] = *reinterpret_cast<const f32x4*>(xb + feat * 16 + 4 * g);       // (zero rows past K0)
     }
     zero_init<NT0>(dx);
-    layer_bwd<NT0, NT0, PAIR>(dz, dx, lds + OFF_T0, lane, id, xT, dW1, db1, rT);  // dx = dX^T
+    layer_bwd<NT0, NT0, PAIR>(dz, dx, lds + IMG::OFF_T0, lane, id, xT, dW1, db1, rT);  // dx = dX^T
     if (dX && live) {
       // row 16 t + 4 g + r: the lane's base (rows 4 g, sample n) once per tile, then a uniform row offset per store (it was a
       // 64-bit multiply-add per lane and store); tiles wholly inside K0 need no lane predicate
@@ -727,7 +623,7 @@ __global__ void mlp_split_reduce_kernel(const float* __restrict__ partial, const
   dy_scale(absmax[0], sc, isc);
   s *= isc;                        // the images are gradients of dY * 2^k: exact power-of-two scaling
   if (e < G_W4) s *= __uint_as_float((uint32_t)(127 - H_PRESCALE_EXP) << 23);   // dW1..3, db1..3 carry the H pre-scale; dW4, db4 do not
-  if (e < G_W2) {
+  if (e < G_W2) {   // (the same ladder as in the sibling file: mlp_split_layout.h says why it is not a shared function)
     const int o = e >> 6, k = e & 63;
     if (k < K0) atomicAdd(&dW0[o * K0 + k], s);
   } else if (e < G_W3) {
@@ -794,20 +690,10 @@ __global__ void mlp_split_pack_kernel(int K0, const float* __restrict__ W0, cons
     const int q = t - im * PER_IMG;
     const int lane = q & 63, s = (q >> 6) & 1, tile = q >> 7;
     const int c = lane & 15, g = lane >> 4, row = 16 * tile + c;
-    const int off[6] = {OFF_W0, OFF_W1, OFF_W2, OFF_T2, OFF_T1, OFF_T0};
+    const int off[6] = {IMG::OFF_W0, IMG::OFF_W1, IMG::OFF_W2, IMG::OFF_T2, IMG::OFF_T1, IMG::OFF_T0};
     float w[8];
 #pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const int k0 = 32 * s + 8 * g + j, kc = kf(s, g, j);
-      switch (im) {
-        case 0: w[j] = k0 < K0 ? W0[row * K0 + k0] : 0.f; break;
-        case 1: w[j] = W1[row * HID + kc]; break;
-        case 2: w[j] = W2[row * HID + kc]; break;
-        case 3: w[j] = W2[kc * HID + row]; break;                 // transposed images: row is an INPUT neuron of the layer
-        case 4: w[j] = W1[kc * HID + row]; break;
-        default: w[j] = row < K0 ? W0[kc * K0 + row] : 0.f; break;
-      }
-    }
+    for (int j = 0; j < 8; j++) w[j] = image_weight(im, row, s, g, j, K0, W0, W1, W2);
     u32x4 hi, lo;
     float wmax = 0.f;
 #pragma unroll
@@ -824,8 +710,8 @@ __global__ void mlp_split_pack_kernel(int K0, const float* __restrict__ W0, cons
     dst[64] = lo;
   } else {
     const int e = t - NTHR;
-    float* tail = reinterpret_cast<float*>(rec + (size_t)off_f32(NT0) * 4);
-    if (e < HID) tail[e] = b0[e];
+    float* tail = reinterpret_cast<float*>(rec + (size_t)IMG::off_f32(NT0) * 4);
+    if (e < HID) tail[e] = b0[e];   // (the same ladder as in the sibling file, see mlp_split_layout.h)
     else if (e < 2 * HID) tail[e] = b1[e - HID];
     else if (e < 3 * HID) tail[e] = b2[e - 2 * HID];
     else if (e < 4 * HID) {
@@ -870,23 +756,19 @@ int psdf_mlp_backward_split_f16_form(void) { return g_f16_form; }
 int psdf_mlp_backward_split_f16(int n_layers, const int* dims, int64_t N, const float* X, const float* const* weights,
                                 const float* const* biases, const float* dY, float* dX, float* const* dW, float* const* db,
                                 void* stream) {
-  if (!dims || !dW || !db || !baseline_split_shape(n_layers, dims, 64, 1)) return PSDF_ERR_UNSUPPORTED;
+  const int rc0 = split_check(n_layers, dims, 64, N, X, weights, biases, dY, dW, db);
+  if (rc0 != PSDF_OK) return rc0;
   const int K0 = dims[0];
   const int rows4 = (K0 + 3) & ~3;
   const int nt0 = K0 <= 48 ? 3 : 4;
   const size_t stage_bytes = (size_t)NWAVES * (64 * 16 + 64) * 4;
-  const size_t img_bytes = img_aligned(nt0);
+  const size_t img_bytes = IMG::aligned(nt0);
   const size_t g_bytes = nt0 == 3 ? (size_t)NWAVES * 2 * NT * 64 * 16 : 0;     // gelu' of the inner layers (see GLDS)
   const size_t lds_bytes = img_bytes + 2 * stage_bytes + g_bytes;              // 159.0 KB (K0 <= 48) / 131.0 KB
   if (lds_bytes > 160 * 1024) return PSDF_ERR_UNSUPPORTED;
-  if (N <= 0 || !X || !weights || !biases || !dY) return PSDF_ERR_ARG;
-  for (int l = 0; l < 4; l++)
-    if (!weights[l] || !biases[l] || !dW[l] || !db[l]) return PSDF_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t ntiles = (N + 15) / 16;
   g_f16_form = 1;
-  int64_t blocks = (ntiles + NWAVES - 1) / NWAVES;   // four tiles in flight per workgroup
-  if (blocks > 256) blocks = 256;  // one workgroup per CU; each wave walks many tiles
+  const int64_t blocks = split_blocks(N);
   const size_t part_bytes = ((size_t)blocks * G_TOTAL * sizeof(float) + 15) & ~(size_t)15;
   // range guard (see RANGE_LIMIT): nets the three-piece bf16 kernel covers (K0 <= 52) get that kernel queued behind this one,
   // conditional on the guard word; wider inputs (53 .. 64: no such kernel) keep the saturating arithmetic and only count the event

@@ -2,6 +2,7 @@
 // formulation (transposed products, chained D->B operand layout, packed LDS weight image).
 #pragma once
 #include "psdf_common.h"
+#include "gelu_device.h"   // vector typedefs, packed helpers, every GELU evaluator
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -55,74 +56,6 @@ constexpr size_t MLP_LDS_MAX = 160 * 1024;  // dynamic LDS a single-wave MLP lau
 // the fp32 forward (mlp_fwd_kernel) stages the whole packed image; launch_fwd and psdf_mlp_supported decline beyond MLP_LDS_MAX
 inline bool fwd_fits(const MlpPlan& p) { return (size_t)p.total * sizeof(float) <= MLP_LDS_MAX; }
 
-// -------------------------------------------------------------------------------------- device math
-// erf with < 1 ulp error, branch-free (both ranges evaluated, then selected): a ~20-instruction VALU
-// sequence instead of the two-branch library erff, which matters because 96 GELUs per lane sit between
-// the MFMA chains of every tile.  Polynomials: the widely used single-precision minimax pair
-// (|x| <= 0.927734375: odd polynomial in x; above: 1 - exp(p(|x|))).
-__device__ __forceinline__ float erf_fast(float a) {
-  const float t = fabsf(a);
-  const float s = a * a;
-  float r = fmaf(-1.72853470e-5f, t, 3.83197126e-4f);
-  float u = fmaf(-3.88396438e-3f, t, 2.42546219e-2f);
-  r = fmaf(r, s, u);
-  r = fmaf(r, t, -1.06777877e-1f);
-  r = fmaf(r, t, -6.34846687e-1f);
-  r = fmaf(r, t, -1.28717512e-1f);
-  r = fmaf(r, t, -t);
-  const float hi = copysignf(1.0f - __expf(r), a);
-  float q = -5.96761703e-4f;
-  q = fmaf(q, s, 4.99119423e-3f);
-  q = fmaf(q, s, -2.67681349e-2f);
-  q = fmaf(q, s, 1.12819925e-1f);
-  q = fmaf(q, s, -3.76125336e-1f);
-  q = fmaf(q, s, 1.28379166e-1f);
-  const float lo = fmaf(q, a, a);
-  return t > 0.927734375f ? hi : lo;
-}
-
-// The same erf on PAIRS of values with packed fp32 arithmetic (v_pk_fma_f32 / v_pk_mul_f32: two lanes' worth of FMA
-// per instruction on gfx950) -- identical operations in identical order, so the results are bit-identical to erf_fast;
-// only the Horner chains (13 of the ~20 instructions) are paired, abs / exp / sign / select stay per element.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x2 splat2(float v) { return f32x2{v, v}; }
-__device__ __forceinline__ f32x2 erf_fast2(f32x2 a) {
-  const f32x2 t = {fabsf(a.x), fabsf(a.y)};
-  const f32x2 s = a * a;
-  f32x2 r = pk_fma(splat2(-1.72853470e-5f), t, splat2(3.83197126e-4f));
-  const f32x2 u = pk_fma(splat2(-3.88396438e-3f), t, splat2(2.42546219e-2f));
-  r = pk_fma(r, s, u);
-  r = pk_fma(r, t, splat2(-1.06777877e-1f));
-  r = pk_fma(r, t, splat2(-6.34846687e-1f));
-  r = pk_fma(r, t, splat2(-1.28717512e-1f));
-  r = pk_fma(r, t, -t);
-  const f32x2 hi = {copysignf(1.0f - __expf(r.x), a.x), copysignf(1.0f - __expf(r.y), a.y)};
-  f32x2 q = splat2(-5.96761703e-4f);
-  q = pk_fma(q, s, splat2(4.99119423e-3f));
-  q = pk_fma(q, s, splat2(-2.67681349e-2f));
-  q = pk_fma(q, s, splat2(1.12819925e-1f));
-  q = pk_fma(q, s, splat2(-3.76125336e-1f));
-  q = pk_fma(q, s, splat2(1.28379166e-1f));
-  const f32x2 lo = pk_fma(q, a, a);
-  return f32x2{t.x > 0.927734375f ? hi.x : lo.x, t.y > 0.927734375f ? hi.y : lo.y};
-}
-__device__ __forceinline__ f32x2 gelu_exact2(f32x2 x) {
-  return (splat2(0.5f) * x) * (splat2(1.0f) + erf_fast2(x * splat2(0.70710678118654752440f)));
-}
-
-__device__ __forceinline__ float gelu_exact(float x) {
-  // torch.nn.GELU() default (erf form): 0.5*x*(1+erf(x/sqrt(2)))
-  return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752440f));
-}
-
-// d/dx gelu(x) = Phi(x) + x*phi(x)
-__device__ __forceinline__ float gelu_grad(float x) {
-  const float cdf = 0.5f * (1.0f + erf_fast(x * 0.70710678118654752440f));
-  const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
-  return fmaf(x, pdf, cdf);
-}
-
 template <int T>
 __device__ __forceinline__ void init_bias(f32x16 (&acc)[T], const float* __restrict__ bias_lds, int h) {
 #pragma unroll
@@ -143,26 +76,7 @@ __device__ __forceinline__ void apply_gelu(f32x16 (&acc)[T]) {
     }
 }
 
-// gelu from ONE exponential and ONE reciprocal (tools/gelu_fit_rational.py): Phi(-|z|) = t P6(t) exp(-z^2/2) with
-// t = 1 / (1 + 0.39 |z|), gelu(z) = max(z, 0) - |z| Phi(-|z|).  14 instructions against ~26 for the erf form; error
-// against float64 1.8e-7 |z| (torch's fp32 formula 0.5 z (1 + erf(z / sqrt 2)) itself: 1.1e-7 |z|) -- both are rounding
-// noise of an fp32 evaluation, and the GPU tests hold the kernels to a multiple of torch's own fp32 error.
-__device__ __forceinline__ float gelu_rational(float z) {
-  const float E = __builtin_amdgcn_exp2f(z * z * -0.72134752044448170368f);
-  const float t = __builtin_amdgcn_rcpf(fmaf(fabsf(z), 0.39f, 1.0f));
-  float q = 5.384693295e-02f;
-  q = fmaf(q, t, -2.582434118e-01f);
-  q = fmaf(q, t, 3.751679361e-01f);
-  q = fmaf(q, t, -1.663514599e-02f);
-  q = fmaf(q, t, 1.944366544e-01f);
-  q = fmaf(q, t, 1.514270604e-01f);
-  const float tail = q * t * E;
-  return fmaf(-fabsf(z), tail, fmaxf(z, 0.f));
-}
-
-// One element per instruction: the form to use beside bf16 MFMAs (packed fp32 arithmetic does not hide in the shadow of
-// the matrix pipe, plain VALU does: tools/mfma_valu_overlap.hip).  The split-bf16 forward is VALU bound (gelu + operand
-// splitting against 156 MFMAs per tile), so it takes the cheaper evaluator: 0.799 -> 0.759 ms for the forward of the bench.
+// gelu_rational on every element, one element per instruction: the split-bf16 forward (why: gelu_device.h)
 template <int T>
 __device__ __forceinline__ void apply_gelu_scalar(f32x16 (&acc)[T]) {
 #pragma unroll
@@ -171,21 +85,7 @@ __device__ __forceinline__ void apply_gelu_scalar(f32x16 (&acc)[T]) {
     for (int r = 0; r < 16; r++) acc[to][r] = gelu_rational(acc[to][r]);
 }
 
-// Two elements per instruction where the instruction set has a packed form (round 5): the two-piece fp16 forward issues 66
-// MFMAs per tile where the bf16 one issues 156, so it is bound by the NUMBER of VALU instructions rather than by what hides
-// beside the matrix pipe -- 9.5 instead of 14 instructions per element.  Same operations in the same order, fused where the
-// scalar form is fused: bit-identical results.  |z| rides as a source modifier of the scalar fmas that need it.
-__device__ __forceinline__ f32x2 gelu_rational2(f32x2 z) {
-  const f32x2 e = (z * z) * f32x2{-0.72134752044448170368f, -0.72134752044448170368f};
-  const f32x2 E = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-  const f32x2 t = {__builtin_amdgcn_rcpf(fmaf(fabsf(z.x), 0.39f, 1.0f)), __builtin_amdgcn_rcpf(fmaf(fabsf(z.y), 0.39f, 1.0f))};
-  f32x2 q = {5.384693295e-02f, 5.384693295e-02f};
-#define PSDF_H2(C) q = __builtin_elementwise_fma(q, t, f32x2{C, C});
-  PSDF_H2(-2.582434118e-01f) PSDF_H2(3.751679361e-01f) PSDF_H2(-1.663514599e-02f) PSDF_H2(1.944366544e-01f) PSDF_H2(1.514270604e-01f)
-#undef PSDF_H2
-  const f32x2 tail = (q * t) * E;
-  return f32x2{fmaf(-fabsf(z.x), tail.x, fmaxf(z.x, 0.f)), fmaf(-fabsf(z.y), tail.y, fmaxf(z.y, 0.f))};
-}
+// gelu_rational2 on pairs: the two-piece fp16 forward (why: gelu_device.h)
 template <int T>
 __device__ __forceinline__ void apply_gelu_packed(f32x16 (&acc)[T]) {
 #pragma unroll
@@ -201,7 +101,6 @@ __device__ __forceinline__ void apply_gelu_packed(f32x16 (&acc)[T]) {
 // out^T = W * in^T for register-resident activations (chained layout, see header).
 // Weight image of a chain layer: [(to,ti)][rq][lane][j] = A operand of k-step r = 4 rq + j, so one 128-bit LDS read
 // per lane (conflict free: consecutive lanes, 16 bytes each) serves four MFMAs.
-typedef float f32x4w __attribute__((ext_vector_type(4)));
 template <int TI, int TO>
 __device__ __forceinline__ void dense_chain(const f32x16 (&in)[TI], f32x16 (&out)[TO], const float* __restrict__ w_lds,
                                             int lane) {
@@ -209,10 +108,10 @@ __device__ __forceinline__ void dense_chain(const f32x16 (&in)[TI], f32x16 (&out
   for (int ti = 0; ti < TI; ti++)
 #pragma unroll
     for (int rq = 0; rq < 4; rq++) {
-      f32x4w a[TO];
+      f32x4 a[TO];
 #pragma unroll
       for (int to = 0; to < TO; to++)
-        a[to] = *reinterpret_cast<const f32x4w*>(w_lds + (((to * TI + ti) * 4 + rq) * 64 + lane) * 4);
+        a[to] = *reinterpret_cast<const f32x4*>(w_lds + (((to * TI + ti) * 4 + rq) * 64 + lane) * 4);
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const float b = in[ti][4 * rq + j];
@@ -232,9 +131,6 @@ __device__ __forceinline__ void dense_chain(const f32x16 (&in)[TI], f32x16 (&out
 // D tile of layer l = B operand of layer l+1.  Lane (sample n = lane & 31, half h = lane >> 5) supplies, for k-step s
 // of input tile ti = s >> 1, its registers r = 8 (s & 1) + j, j = 0..7, i.e. the neurons 32 ti + row_of(r, h); the
 // weight image is permuted to match.  Layer 0 reads features k = 16 s + 8 h + j of the feature-major input.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SPLIT_LDS_MAX = 80 * 1024;  // two workgroups per CU
 
 struct SplitPlan {
@@ -317,12 +213,12 @@ __device__ __forceinline__ void split8(const float (&x)[8], bf16x8& p1, bf16x8& 
 // (every bias block of the split image starts on a 16-byte boundary)
 template <int T>
 __device__ __forceinline__ void init_bias4(f32x16 (&acc)[T], const float* __restrict__ bias_lds, int h) {
-  const f32x4w* __restrict__ b4 = reinterpret_cast<const f32x4w*>(bias_lds);
+  const f32x4* __restrict__ b4 = reinterpret_cast<const f32x4*>(bias_lds);
 #pragma unroll
   for (int to = 0; to < T; to++)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      const f32x4w v = b4[8 * to + 2 * q + h];
+      const f32x4 v = b4[8 * to + 2 * q + h];
 #pragma unroll
       for (int c = 0; c < 4; c++) acc[to][4 * q + c] = v[c];
     }
@@ -334,8 +230,8 @@ __device__ __forceinline__ void init_bias4(f32x16 (&acc)[T], const float* __rest
 // Half the MFMAs and about half the splitting work of the three-piece bf16 scheme; gfx950's matrix pipe honours fp16 subnormals
 // (attic/prototypes/mlp_fwd_split_f16.hip), so small low pieces keep an absolute precision of 2^-24; values must stay below 65504.
 // The image keeps the three-slot record layout (slot 2 unused), so SplitPlan is shared.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2v_t __attribute__((ext_vector_type(2)));
+// (One of three two-piece splits kept apart on purpose: split2 in mlp_bwd_split_f16.hip is the fma-mix form and needs
+// -fno-slp-vectorize, wsplit2 in mlp_wide.hip the subtract-and-convert form on a pair; same pieces, different instructions.)
 __device__ __forceinline__ void split8h(const float (&x)[8], f16x8& hi, f16x8& lo) {
   u32x4 qh, ql;
 #pragma unroll
@@ -405,6 +301,5 @@ __device__ __forceinline__ void split_chain(const f32x16 (&in)[TI], f32x16 (&out
     split_mac<TO, F16>(out, x, w + s * 192, 2 * TI, lane);
   }
 }
-
 
 }  // namespace

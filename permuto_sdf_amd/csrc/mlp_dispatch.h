@@ -70,8 +70,8 @@ inline bool wide_backward_shape(int n_layers, const int* d) {
 }
 
 // ---- the BASELINE net {K0, 64, 64, 64, out} with 1 <= K0 <= max_k0, 1 <= out <= max_out: the two-piece fp16 image of
-// psdf_mlp_pack_f16 and psdf_mlp_forward_f16 (64, 4), the split backward kernels psdf_mlp_backward_split(_f16) (64, 1; their
-// LDS check narrows the bf16 one to K0 <= 52)
+// psdf_mlp_pack_f16 and psdf_mlp_forward_f16 (64, 4), the split backward kernels (split_check of mlp_split_layout.h):
+// psdf_mlp_backward_split_f16 (64, 1), psdf_mlp_backward_split (52, 1: what its larger image leaves of 160 KB of LDS)
 inline bool baseline_split_shape(int n_layers, const int* d, int max_k0, int max_out) {
   return n_layers == 4 && d[0] >= 1 && d[0] <= max_k0 && d[1] == 64 && d[2] == 64 && d[3] == 64 && d[4] >= 1 && d[4] <= max_out;
 }

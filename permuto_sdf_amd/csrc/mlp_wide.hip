@@ -16,8 +16,7 @@
 //   * fp32 MFMA (v_mfma_f32_16x16x4_f32): exact fp32 products, no operand splitting; the batch is ~49 k samples per step, the
 //     kernel is latency / launch bound, not matrix bound.
 // One barrier per layer and direction (8 per tile).
-#include "psdf_common.h"
-#include "mlp_dispatch.h"
+#include "mlp_split_layout.h"   // kf; with it gelu_device.h (typedefs, gelu_erf, gelu_rational4), mlp_dispatch.h
 #include <stdio.h>
 #include <stdlib.h>
 #include <atomic>
@@ -26,38 +25,11 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 constexpr int WN = 8;        // waves per workgroup
 constexpr int TS = 32;       // samples per workgroup tile (two 16-sample MFMA column blocks)
 constexpr int RS = 36;       // LDS row stride in floats (144 B: 128-bit reads of 16 consecutive rows spread over the banks)
-
-__device__ __forceinline__ float erf_w(float a) {   // < 1 ulp (same polynomial as mlp_device.h)
-  const float t = fabsf(a), s = a * a;
-  float r = fmaf(-1.72853470e-5f, t, 3.83197126e-4f);
-  float u = fmaf(-3.88396438e-3f, t, 2.42546219e-2f);
-  r = fmaf(r, s, u);
-  r = fmaf(r, t, -1.06777877e-1f);
-  r = fmaf(r, t, -6.34846687e-1f);
-  r = fmaf(r, t, -1.28717512e-1f);
-  r = fmaf(r, t, -t);
-  const float hi = copysignf(1.0f - __expf(r), a);
-  float q = -5.96761703e-4f;
-  q = fmaf(q, s, 4.99119423e-3f);
-  q = fmaf(q, s, -2.67681349e-2f);
-  q = fmaf(q, s, 1.12819925e-1f);
-  q = fmaf(q, s, -3.76125336e-1f);
-  q = fmaf(q, s, 1.28379166e-1f);
-  const float lo = fmaf(q, a, a);
-  return t > 0.927734375f ? hi : lo;
-}
-__device__ __forceinline__ void gelu_both_w(float z, float& h, float& gp) {
-  const float cdf = fmaf(0.5f, erf_w(z * 0.70710678118654752440f), 0.5f);
-  const float pdf = 0.3989422804014327f * __expf(-0.5f * z * z);
-  h = z * cdf;
-  gp = fmaf(z, pdf, cdf);
-}
 
 struct WideArgs {
   const float* W[4];    // normalised weights, row major [out][in_pad]  (in_pad = 16 * tiles of the input)
@@ -97,7 +69,7 @@ __device__ __forceinline__ void layer_fwd(const float* __restrict__ W, int in_pa
     for (int r = 0; r < 4; r++) {
       const int row = 16 * t + 4 * g + r;
       float h = acc[sb][r], gp = 1.f;
-      if (ACT) gelu_both_w(acc[sb][r], h, gp);
+      if (ACT) gelu_erf(acc[sb][r], h, gp);
       H[row * RS + 16 * sb + c] = h;
       if (G) G[row * RS + 16 * sb + c] = gp;
     }
@@ -583,28 +555,25 @@ int wide_forward(const int* dims, int64_t N, const float* X, const float* const*
 //     (H[:, n] * 2^(kmin - k(n)), kmin = the tile's smallest k) and the tile's accumulators are folded into the running sums with
 //     2^-kmin -- no second pass over dY, no extra launch.
 // Same gradient image, same summing launch as the fp32 kernel.  Accuracy: tests/test_gpu_mlp.py::test_wide_net_backward_*.
-typedef _Float16 wf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 wh2 __attribute__((ext_vector_type(2)));
-typedef float wf32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t wu32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t wu32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #define MFMA16H(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-__host__ __device__ inline int wkf(int s, int g, int j) { return 32 * s + 16 * (j >> 2) + 4 * g + (j & 3); }
-// two fp32 -> packed high pieces, packed low pieces (element 0 in the low half)
+// two fp32 -> packed high pieces, packed low pieces (element 0 in the low half).  (One of three two-piece splits kept apart on
+// purpose: split2 in mlp_bwd_split_f16.hip is the fma-mix form and needs -fno-slp-vectorize, split8h in mlp_device.h works on
+// eight values; same pieces, different instructions.)
 __device__ __forceinline__ void wsplit2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
-  const wh2 h = __builtin_convertvector(wf32x2{x0, x1}, wh2);      // v_cvt_pk_f16_f32: nearest even
-  const wf32x2 r = wf32x2{x0, x1} - wf32x2{(float)h[0], (float)h[1]};   // exact
-  const wh2 l = __builtin_convertvector(r, wh2);
+  const h2v_t h = __builtin_convertvector(f32x2{x0, x1}, h2v_t);      // v_cvt_pk_f16_f32: nearest even
+  const f32x2 r = f32x2{x0, x1} - f32x2{(float)h[0], (float)h[1]};   // exact
+  const h2v_t l = __builtin_convertvector(r, h2v_t);
   hi = __builtin_bit_cast(uint32_t, h);
   lo = __builtin_bit_cast(uint32_t, l);
 }
 struct WRec {   // the two pieces of one 8-slot operand
-  wf16x8 p[2];
+  f16x8 p[2];
 };
-__device__ __forceinline__ WRec wload(const wu32x4* __restrict__ r) {   // r -> piece 0 of the lane's record; piece 1 is 64 records on
+__device__ __forceinline__ WRec wload(const u32x4* __restrict__ r) {   // r -> piece 0 of the lane's record; piece 1 is 64 records on
   WRec o;
-  o.p[0] = __builtin_bit_cast(wf16x8, r[0]);
-  o.p[1] = __builtin_bit_cast(wf16x8, r[64]);
+  o.p[0] = __builtin_bit_cast(f16x8, r[0]);
+  o.p[1] = __builtin_bit_cast(f16x8, r[64]);
   return o;
 }
 __device__ __forceinline__ f32x4 wmac3(const WRec& a, const WRec& b, f32x4 acc) {   // a0 b0 + a0 b1 + a1 b0
@@ -614,36 +583,9 @@ __device__ __forceinline__ f32x4 wmac3(const WRec& a, const WRec& b, f32x4 acc) 
   return acc;
 }
 
-// gelu and gelu' of four values from ONE exponential and ONE reciprocal each (the fit of csrc/mlp_bwd_split_f16.hip: E = exp(-z^2/2),
-// t = 1 / (1 + 0.39 |z|), Phi(-|z|) = t P6(t) E; errors 1.8e-7 |z| and 1.9e-7 against float64), two packed pairs side by side
-__device__ __forceinline__ wf32x2 wfma2(wf32x2 a, wf32x2 b, wf32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ wf32x2 wsp2(float v) { return wf32x2{v, v}; }
-__device__ __forceinline__ void wgelu4(const f32x4& z, f32x4& h, f32x4& gp) {
-  const wf32x2 za = {z[0], z[1]}, zb = {z[2], z[3]};
-  const wf32x2 ea = (za * za) * wsp2(-0.72134752044448170368f), eb = (zb * zb) * wsp2(-0.72134752044448170368f);
-  const wf32x2 Ea = {__builtin_amdgcn_exp2f(ea.x), __builtin_amdgcn_exp2f(ea.y)};
-  const wf32x2 Eb = {__builtin_amdgcn_exp2f(eb.x), __builtin_amdgcn_exp2f(eb.y)};
-  const wf32x2 da = {__builtin_fmaf(__builtin_fabsf(za.x), 0.39f, 1.0f), __builtin_fmaf(__builtin_fabsf(za.y), 0.39f, 1.0f)};
-  const wf32x2 db = {__builtin_fmaf(__builtin_fabsf(zb.x), 0.39f, 1.0f), __builtin_fmaf(__builtin_fabsf(zb.y), 0.39f, 1.0f)};
-  const wf32x2 ta = {__builtin_amdgcn_rcpf(da.x), __builtin_amdgcn_rcpf(da.y)};
-  const wf32x2 tb = {__builtin_amdgcn_rcpf(db.x), __builtin_amdgcn_rcpf(db.y)};
-  wf32x2 qa = wsp2(5.384693295e-02f), qb = wsp2(5.384693295e-02f);
-#define WHORNER(C) qa = wfma2(qa, ta, wsp2(C)); qb = wfma2(qb, tb, wsp2(C));
-  WHORNER(-2.582434118e-01f) WHORNER(3.751679361e-01f) WHORNER(-1.663514599e-02f) WHORNER(1.944366544e-01f) WHORNER(1.514270604e-01f)
-#undef WHORNER
-  const wf32x2 la = (qa * ta) * Ea, lb = (qb * tb) * Eb;
-  const wf32x2 ma = wsp2(0.5f) - la, mb = wsp2(0.5f) - lb;
-  const wf32x2 ca = wf32x2{__builtin_copysignf(ma.x, za.x), __builtin_copysignf(ma.y, za.y)} + wsp2(0.5f);
-  const wf32x2 cb = wf32x2{__builtin_copysignf(mb.x, zb.x), __builtin_copysignf(mb.y, zb.y)} + wsp2(0.5f);
-  const wf32x2 ha = za * ca, hb = zb * cb;
-  const wf32x2 ga = wfma2(za, Ea * wsp2(0.3989422804014327f), ca), gb = wfma2(zb, Eb * wsp2(0.3989422804014327f), cb);
-  h = f32x4{ha.x, ha.y, hb.x, hb.y};
-  gp = f32x4{ga.x, ga.y, gb.x, gb.y};
-}
-
 struct WideArgsH {
-  const wu32x4* A[4];    // forward weight records of layer l: [out tile][k-step][piece][lane]
-  const wu32x4* AT[4];   // transposed: [in tile][k-step over the outputs][piece][lane]
+  const u32x4* A[4];    // forward weight records of layer l: [out tile][k-step][piece][lane]
+  const u32x4* AT[4];   // transposed: [in tile][k-step over the outputs][piece][lane]
   const float* b[4];
   int dims[5];
   uint32_t* guard;       // range guard of the stream (wide_guard_word): set to `token`, the number of THIS launch, when raised; the
@@ -675,8 +617,8 @@ __device__ __forceinline__ void wide_report(float m, uint32_t* guard, uint32_t t
 struct PackH {
   int out[4], in[4], out_tiles[4], in_tiles[4];
   const float* W[4];
-  wu32x4* A[4];
-  wu32x4* AT[4];
+  u32x4* A[4];
+  u32x4* AT[4];
   uint32_t* guard;      // as in WideArgsH
   uint32_t token;
   uint32_t* sticky;
@@ -693,11 +635,11 @@ __global__ void mlp_wide_f16_pack_kernel(PackH p) {
   float w[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) {
-    const int k = wkf(s, g, j);
+    const int k = kf(s, g, j);
     const int o = tr ? k : row, i = tr ? row : k;
     w[j] = (o < p.out[l] && i < p.in[l]) ? p.W[l][o * p.in[l] + i] : 0.f;
   }
-  wu32x4 hi, lo;
+  u32x4 hi, lo;
   float wmax = 0.f;
 #pragma unroll
   for (int q = 0; q < 4; q++) {
@@ -711,7 +653,7 @@ __global__ void mlp_wide_f16_pack_kernel(PackH p) {
     if (p.guard) atomicExch(p.guard, p.token);
     if (p.sticky) atomicOr(p.sticky, 1u);
   }
-  wu32x4* dst = (tr ? p.AT[l] : p.A[l]) + ((size_t)(t * ks + s) * 2) * 64 + lane;
+  u32x4* dst = (tr ? p.AT[l] : p.A[l]) + ((size_t)(t * ks + s) * 2) * 64 + lane;
   dst[0] = hi;
   dst[64] = lo;
 }
@@ -728,20 +670,20 @@ __global__ void __launch_bounds__(WN * 64, 1)
                             float* __restrict__ dX, float* __restrict__ partial) {
   static_assert(TI0 <= WN && T1 <= WN && T2 <= WN && T3 <= WN && T4 <= WN, "one output tile per wave and layer");
   constexpr int NS0 = wns(TI0), NS1 = wns(T1), NS2 = wns(T2), NS3 = wns(T3), NS4 = wns(T4);
-  extern __shared__ __align__(16) wu32x4 wl[];
+  extern __shared__ __align__(16) u32x4 wl[];
   // B records: [k-step][sample block 2][piece 2][lane 64] = 256 records per k-step
-  wu32x4* B0 = wl;                       // inputs
-  wu32x4* B1 = B0 + NS0 * 256;           // h1, later dZ1
-  wu32x4* B2 = B1 + NS1 * 256;
-  wu32x4* B3 = B2 + NS2 * 256;
-  wu32x4* B4 = B3 + NS3 * 256;           // the (scaled) upstream gradient
+  u32x4* B0 = wl;                       // inputs
+  u32x4* B1 = B0 + NS0 * 256;           // h1, later dZ1
+  u32x4* B2 = B1 + NS1 * 256;
+  u32x4* B3 = B2 + NS2 * 256;
+  u32x4* B4 = B3 + NS3 * 256;           // the (scaled) upstream gradient
   // T records: [tile][piece 2][lane 64] = 128 records per tile
-  wu32x4* X0T = B4 + NS4 * 256;
-  wu32x4* H1T = X0T + TI0 * 128;
-  wu32x4* H2T = H1T + T1 * 128;
-  wu32x4* H3T = H2T + T2 * 128;
-  wu32x4* SCR = H3T + T3 * 128;          // per wave: the dZ side of its own dW rows, [piece 2][lane 64]
-  wu32x4* YST = SCR + 2 * WN * 128;      // [T4][8][64] floats: the staged upstream gradient of the next tile
+  u32x4* X0T = B4 + NS4 * 256;
+  u32x4* H1T = X0T + TI0 * 128;
+  u32x4* H2T = H1T + T1 * 128;
+  u32x4* H3T = H2T + T2 * 128;
+  u32x4* SCR = H3T + T3 * 128;          // per wave: the dZ side of its own dW rows, [piece 2][lane 64]
+  u32x4* YST = SCR + 2 * WN * 128;      // [T4][8][64] floats: the staged upstream gradient of the next tile
   float* MSC = reinterpret_cast<float*>(YST + T4 * 128);        // [T4][32]: per output tile, the largest |dY| of a sample
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int K0 = a.dims[0], OUT = a.dims[4];
@@ -771,19 +713,19 @@ __global__ void __launch_bounds__(WN * 64, 1)
   const int64_t ntiles = (N + TS - 1) / TS;
 
   // a tile of values in D layout (v[sb][r] = feature 16 t + 4 g + r, sample 16 sb + c) -> its slots of the B records of `Breg`
-  auto put_b = [&](wu32x4* Breg, int t, const f32x4 (&v)[2]) {
+  auto put_b = [&](u32x4* Breg, int t, const f32x4 (&v)[2]) {
 #pragma unroll
     for (int sb = 0; sb < 2; sb++) {
       uint32_t h0, l0, h1, l1;
       wsplit2(v[sb][0], v[sb][1], h0, l0);
       wsplit2(v[sb][2], v[sb][3], h1, l1);
-      wu32x2* rec = reinterpret_cast<wu32x2*>(Breg + ((t >> 1) * 2 + sb) * 128 + lane) + (t & 1);
-      rec[0] = wu32x2{h0, h1};
-      rec[128] = wu32x2{l0, l1};      // piece 1: 64 records = 128 half records on
+      u32x2* rec = reinterpret_cast<u32x2*>(Breg + ((t >> 1) * 2 + sb) * 128 + lane) + (t & 1);
+      rec[0] = u32x2{h0, h1};
+      rec[128] = u32x2{l0, l1};      // piece 1: 64 records = 128 half records on
     }
   };
   // four features (4 g + r of a tile) of the lane's sample 16 sb + c, transposed, into the T records at `Treg` (2 x 64 records)
-  auto put_t1 = [&](wu32x4* Treg, int sb, const f32x4& v) {
+  auto put_t1 = [&](u32x4* Treg, int sb, const f32x4& v) {
     _Float16* base = reinterpret_cast<_Float16*>(Treg);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -794,7 +736,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
       base[64 * 8 + idx] = l;
     }
   };
-  auto put_t = [&](wu32x4* Treg, const f32x4 (&v)[2]) {
+  auto put_t = [&](u32x4* Treg, const f32x4 (&v)[2]) {
     put_t1(Treg, 0, v[0]);
     put_t1(Treg, 1, v[1]);
   };
@@ -822,7 +764,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
       float* dst = reinterpret_cast<float*>(B0 + wave * 128);
 #pragma unroll
       for (int j = 0; j < 8; j++) {
-        int row = wkf(s, g, j);
+        int row = kf(s, g, j);
         row = row < K0 ? row : K0 - 1;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(X + (int64_t)row * N + n),
                                          (__attribute__((address_space(3))) void*)(dst + j * 64), 4, 0, 0);
@@ -849,7 +791,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
     const int s = (wave < NS0 * 2 ? wave : 0) >> 1, sbx = wave & 1;
     const float* srcx = reinterpret_cast<const float*>(B0 + (wave < NS0 * 2 ? wave : 0) * 128);
 #pragma unroll
-    for (int j = 0; j < 8; j++) px[j] = (wkf(s, g, j) < K0 && m0 + 16 * sbx + c < N) ? srcx[j * 64 + lane] : 0.f;
+    for (int j = 0; j < 8; j++) px[j] = (kf(s, g, j) < K0 && m0 + 16 * sbx + c < N) ? srcx[j * 64 + lane] : 0.f;
     const float* srcy = reinterpret_cast<const float*>(YST + (wave < T4 ? wave : 0) * 128);
 #pragma unroll
     for (int sb = 0; sb < 2; sb++)
@@ -931,7 +873,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
         x[j] = px[j];
         vmax = fmaxf(vmax, fabsf(x[j]) * (float)(1 << PRE_X));
       }
-      wu32x4 hi, lo;
+      u32x4 hi, lo;
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         uint32_t h, l;
@@ -939,7 +881,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
         hi[j] = h;
         lo[j] = l;
       }
-      wu32x4* rec = B0 + (s * 2 + sb) * 128 + lane;
+      u32x4* rec = B0 + (s * 2 + sb) * 128 + lane;
       rec[0] = hi;
       rec[64] = lo;
       const float f = hs_x[sb];
@@ -965,9 +907,9 @@ __global__ void __launch_bounds__(WN * 64, 1)
       if (wave == WN - 1) {
 #pragma unroll
         for (int sb = 0; sb < 2; sb++) {
-          wu32x2* rec = reinterpret_cast<wu32x2*>(B4 + ((NS4 - 1) * 2 + sb) * 128 + lane) + 1;
-          rec[0] = wu32x2{0u, 0u};
-          rec[128] = wu32x2{0u, 0u};
+          u32x2* rec = reinterpret_cast<u32x2*>(B4 + ((NS4 - 1) * 2 + sb) * 128 + lane) + 1;
+          rec[0] = u32x2{0u, 0u};
+          rec[128] = u32x2{0u, 0u};
         }
       }
     }
@@ -977,21 +919,21 @@ __global__ void __launch_bounds__(WN * 64, 1)
     // (the first two k-steps: 16 registers; the other two are requested when the phase starts and arrive under the first MFMAs --
     //  all four ahead cost 32 registers that the kernel, at 256 per wave, does not have)
     WRec wq[2];
-    const wu32x4* wnext = nullptr;     // the records the current prefetch belongs to (k-steps 2, 3 follow from it)
-    auto prefetch = [&](const wu32x4* Aw, int ns, int tiles) {
+    const u32x4* wnext = nullptr;     // the records the current prefetch belongs to (k-steps 2, 3 follow from it)
+    auto prefetch = [&](const u32x4* Aw, int ns, int tiles) {
       // (the lane index behind an empty asm: left visible, the eight record addresses of a tile are hoisted out of the tile loop as
       //  64-bit register pairs, parked in scratch, and their reloads wait -- vmcnt counts in order -- for the LDS-DMA prefetch of
       //  the next tile that is in flight by then; recomputed here they are two instructions each)
       int lane_p = lane;
       asm volatile("" : "+v"(lane_p));
-      wnext = reinterpret_cast<const wu32x4*>(reinterpret_cast<const char*>(Aw) + (uint32_t)((wave * ns * 128 + lane_p) * 16));
+      wnext = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(Aw) + (uint32_t)((wave * ns * 128 + lane_p) * 16));
 #pragma unroll
       for (int s = 0; s < 2; s++)
         if (s < ns && wave < tiles) wq[s] = wload(wnext + (size_t)s * 128);
     };
     // acc = (bias +) sum over the k-steps of  weight records x B records
-    auto mma = [&](int ns, const wu32x4* Bin, f32x4 (&acc)[2]) {
-      const wu32x4* wcur = wnext;
+    auto mma = [&](int ns, const u32x4* Bin, f32x4 (&acc)[2]) {
+      const u32x4* wcur = wnext;
       WRec w23[2];
 #pragma unroll
       for (int s = 2; s < 4; s++)
@@ -1015,11 +957,11 @@ __global__ void __launch_bounds__(WN * 64, 1)
     };
     const f32x4 zero2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     // pre-activations -> activation (B records, scaled T records) and gelu' (kept)
-    auto act = [&](f32x4 (&acc)[2], wu32x4* Bout, wu32x4* Tout, f32x4 (&gp)[2], bool odd_pad, int tiles_out) {
+    auto act = [&](f32x4 (&acc)[2], u32x4* Bout, u32x4* Tout, f32x4 (&gp)[2], bool odd_pad, int tiles_out) {
       f32x4 h[2], hsc[2];
 #pragma unroll
       for (int sb = 0; sb < 2; sb++) {
-        wgelu4(acc[sb], h[sb], gp[sb]);
+        gelu_rational4(acc[sb], h[sb], gp[sb]);
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           hsc[sb][r] = h[sb][r] * hs_h[sb];
@@ -1034,7 +976,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
     };
     // dW rows of the own tile: dZ^T (own scratch) x H^T (T records), folded into the running sums
     // (the scratch was written before the last barrier, by the wave that owns the tile in the chain)
-    auto dw = [&](const wu32x4* Sset, const wu32x4* Tin, int tout, int tin, int cn, f32x4* run, float fold) {
+    auto dw = [&](const u32x4* Sset, const u32x4* Tin, int tout, int tin, int cn, f32x4* run, float fold) {
       const int sl = wave / tout, to = wave - sl * tout;       // slice of the columns, row tile
       const WRec za = wload(Sset + to * 128 + lane);
       for (int i = 0; i < cn; i++) {
@@ -1047,7 +989,7 @@ __global__ void __launch_bounds__(WN * 64, 1)
       }
     };
     // dH (of the own tile of the layer below) times gelu' -> dZ: B records (in place of the activation's), scratch, bias sums
-    auto to_dz = [&](f32x4 (&acc)[2], const f32x4 (&gp)[2], f32x4& db, wu32x4* Bout, wu32x4* Sset, bool odd_pad, int tiles) {
+    auto to_dz = [&](f32x4 (&acc)[2], const f32x4 (&gp)[2], f32x4& db, u32x4* Bout, u32x4* Sset, bool odd_pad, int tiles) {
 #pragma unroll
       for (int sb = 0; sb < 2; sb++)
 #pragma unroll
@@ -1089,10 +1031,10 @@ __global__ void __launch_bounds__(WN * 64, 1)
     __syncthreads();
     WDBG
     // (the two scratch sets alternate layer by layer, starting with set A for the linear layer's upstream gradient)
-    wu32x4* const SA = SCR;
-    wu32x4* const SB = SCR + WN * 128;
-    wu32x4* const S2set = L3 ? SA : SB;       // where dZ2 (transposed) goes; dZ1 takes the other set
-    wu32x4* const S1set = L3 ? SB : SA;
+    u32x4* const SA = SCR;
+    u32x4* const SB = SCR + WN * 128;
+    u32x4* const S2set = L3 ? SA : SB;       // where dZ2 (transposed) goes; dZ1 takes the other set
+    u32x4* const S1set = L3 ? SB : SA;
     if constexpr (L3) {
       if (wave < T3) {
         bias_init(a.b[2], a.dims[3], acc);
@@ -1191,24 +1133,24 @@ __global__ void __launch_bounds__(WN * 64, 2)
   static_assert(TI0 <= WN && T1 <= WN && T2 <= WN && T3 <= WN && T4 <= WN && wns(TI0) * 2 <= WN, "one output tile per wave and layer");
   constexpr int NS0 = wns(TI0), NS1 = wns(T1), NS2 = wns(T2), NS3 = wns(T3);
   static_assert(NS0 <= 4 && NS1 <= 4 && NS2 <= 4 && NS3 <= 4, "four k-steps of weight records per phase");
-  extern __shared__ __align__(16) wu32x4 wl[];
-  wu32x4* B0 = wl;
-  wu32x4* B1 = B0 + NS0 * 256;
-  wu32x4* B2 = B1 + NS1 * 256;
-  wu32x4* B3 = B2 + NS2 * 256;
+  extern __shared__ __align__(16) u32x4 wl[];
+  u32x4* B0 = wl;
+  u32x4* B1 = B0 + NS0 * 256;
+  u32x4* B2 = B1 + NS1 * 256;
+  u32x4* B3 = B2 + NS2 * 256;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int K0 = a.dims[0], OUT = a.dims[4];
   const int64_t ntiles = (N + TS - 1) / TS;
   float vmax = 0.f;
-  auto put_b = [&](wu32x4* Breg, int t, const f32x4 (&v)[2]) {
+  auto put_b = [&](u32x4* Breg, int t, const f32x4 (&v)[2]) {
 #pragma unroll
     for (int sb = 0; sb < 2; sb++) {
       uint32_t h0, l0, h1, l1;
       wsplit2(v[sb][0], v[sb][1], h0, l0);
       wsplit2(v[sb][2], v[sb][3], h1, l1);
-      wu32x2* rec = reinterpret_cast<wu32x2*>(Breg + ((t >> 1) * 2 + sb) * 128 + lane) + (t & 1);
-      rec[0] = wu32x2{h0, h1};
-      rec[128] = wu32x2{l0, l1};
+      u32x2* rec = reinterpret_cast<u32x2*>(Breg + ((t >> 1) * 2 + sb) * 128 + lane) + (t & 1);
+      rec[0] = u32x2{h0, h1};
+      rec[128] = u32x2{l0, l1};
     }
   };
   auto request = [&](int64_t t2) {      // the next tile's inputs by LDS-DMA into the wave's own 2 KB of the input records (see the backward)
@@ -1223,7 +1165,7 @@ __global__ void __launch_bounds__(WN * 64, 2)
       float* dst = reinterpret_cast<float*>(B0 + wave * 128);
 #pragma unroll
       for (int j = 0; j < 8; j++) {
-        int row = wkf(s, g2, j);
+        int row = kf(s, g2, j);
         row = row < K0 ? row : K0 - 1;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(X + (int64_t)row * N + n),
                                          (__attribute__((address_space(3))) void*)(dst + j * 64), 4, 0, 0);
@@ -1242,10 +1184,10 @@ __global__ void __launch_bounds__(WN * 64, 2)
       float x[8];
 #pragma unroll
       for (int j = 0; j < 8; j++) {
-        x[j] = (wkf(s, g, j) < K0 && n0 + 16 * sb + c < N) ? src[j * 64 + lane] : 0.f;
+        x[j] = (kf(s, g, j) < K0 && n0 + 16 * sb + c < N) ? src[j * 64 + lane] : 0.f;
         vmax = fmaxf(vmax, fabsf(x[j]));
       }
-      wu32x4 hi, lo;
+      u32x4 hi, lo;
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         uint32_t h, l;
@@ -1253,11 +1195,11 @@ __global__ void __launch_bounds__(WN * 64, 2)
         hi[j] = h;
         lo[j] = l;
       }
-      wu32x4* rec = B0 + (s * 2 + sb) * 128 + lane;
+      u32x4* rec = B0 + (s * 2 + sb) * 128 + lane;
       rec[0] = hi;
       rec[64] = lo;
     }
-    auto layer = [&](const wu32x4* Aw, const float* bias, int out_true, int ns, int tiles, const wu32x4* Bin, f32x4 (&acc)[2]) {
+    auto layer = [&](const u32x4* Aw, const float* bias, int out_true, int ns, int tiles, const u32x4* Bin, f32x4 (&acc)[2]) {
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int row = 16 * wave + 4 * g + r;
@@ -1278,12 +1220,12 @@ __global__ void __launch_bounds__(WN * 64, 2)
           }
       }
     };
-    auto act = [&](f32x4 (&acc)[2], wu32x4* Bout, int tiles) {
+    auto act = [&](f32x4 (&acc)[2], u32x4* Bout, int tiles) {
       if (wave < tiles) {
         f32x4 h[2], gp;
 #pragma unroll
         for (int sb = 0; sb < 2; sb++) {
-          wgelu4(acc[sb], h[sb], gp);
+          gelu_rational4(acc[sb], h[sb], gp);
 #pragma unroll
           for (int r = 0; r < 4; r++) vmax = fmaxf(vmax, fabsf(h[sb][r]));
         }
@@ -1401,7 +1343,7 @@ int wide_launch_f16(int n_layers, const int* dims, int64_t N, const float* X, co
   char* redo_scratch = scratch + main_bytes;
   WideArgsH a;
   PackH pk;
-  wu32x4* wp = reinterpret_cast<wu32x4*>(scratch);
+  u32x4* wp = reinterpret_cast<u32x4*>(scratch);
   int nmax = 1;
   for (int l = 0; l < 4; l++) {
     const bool have = src[l] >= 0;
@@ -1461,7 +1403,7 @@ int wide_forward_f16(const int* dims, int64_t N, const float* X, const float* co
   const uint32_t token = wide_guard_token();
   WideArgsH a;
   PackH pk;
-  wu32x4* wp = reinterpret_cast<wu32x4*>(scratch);
+  u32x4* wp = reinterpret_cast<u32x4*>(scratch);
   int nmax = 0;
   for (int l = 0; l < 4; l++) {
     pk.out[l] = dims[l + 1], pk.in[l] = dims[l], pk.out_tiles[l] = tiles[l + 1], pk.in_tiles[l] = tiles[l];
