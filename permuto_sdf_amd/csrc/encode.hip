@@ -12,12 +12,14 @@
 // Launch shape: grid (ceil(N/256), Lt), one thread per (point, level).  blockIdx.x is the fast dispatch
 // dimension, so the chip sweeps one level's 2-MiB table at a time and that table stays resident in every
 // XCD's 4-MiB L2 (the gathers are L2 hits, HBM sees positions + outputs only).
-#include <cstdlib>
 #include <cstdio>
-#include "encode_device.h"
-#include <vector>
-#include <mutex>
 #include <cstring>
+#include <mutex>
+#include <type_traits>
+#include <vector>
+
+#include "encode_device.h"
+#include "encode_plan.h"
 
 namespace {
 
@@ -271,7 +273,7 @@ struct Queues {
   int* tails;      // [L, NP]           zeroed per call
   int cap, np, shift;  // rows per partition = 1 << shift
 };
-constexpr int Q_MAX_PARTS = 64;
+using psdf::enc_plan::Q_MAX_PARTS;   // encode_plan.h: the queue plan is sized by it
 constexpr int Q_LDS_INTS = 4 * Q_MAX_PARTS + 4;   // q_cnt, q_base, q_off (+1), q_gd; 3 vote words
 
 // Workgroup-collective append of up to NC contributions per thread to the level's partition queues.
@@ -1059,54 +1061,398 @@ EncConv& enc_conv_state() {
 }
 }  // namespace psdf
 
-// ================================================================================== C ABI
-// Position gradient only: the level-group kernel + the slab reduction when stream-ordered scratch is available (not while a
-// graph is being captured: there the float-atomic form runs), PSDF_ENC_POS_ATOMICS=1 forces the atomic form (A/B).
-template <int P_, int F_, int POS_LPB>
-static void launch_bwd_pos_lpb(int64_t N, int nr_levels, int Lt, int capacity, const float* positions, const float* lattice,
-                               const float* scale_factor, const float* shifts, const float* window, float points_scaling, int pad,
-                               const float* grad_sliced, const unsigned char* skip, float* grad_positions, hipStream_t st,
-                               bool capturing) {
-  static const bool force_atomics = getenv("PSDF_ENC_POS_ATOMICS") && atoi(getenv("PSDF_ENC_POS_ATOMICS")) != 0;
-  const unsigned nb = psdf_blocks(N, PSDF_BLOCK);
-  const int groups = (Lt + POS_LPB - 1) / POS_LPB;
+// ================================================================================== host layer
+// Ordinary C++ between the C ABI and the kernels: one list of the supported (P, F) pairs, one bundle of the arguments every
+// kernel takes, one function template per launch.  The arithmetic that sizes the launches is in encode_plan.h.
+namespace {
+namespace plan = psdf::enc_plan;
+using plan::env_int;
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// The supported (pos_dim, nr_feat) pairs: fn(int_c<P>, int_c<F>) for the one that matches.
+template <class Fn>
+int dispatch_pf(int pos_dim, int nr_feat, Fn&& fn) {
+  if (pos_dim == 3 && nr_feat == 2) return fn(int_c<3>{}, int_c<2>{});
+  if (pos_dim == 4 && nr_feat == 2) return fn(int_c<4>{}, int_c<2>{});
+  if (pos_dim == 2 && nr_feat == 2) return fn(int_c<2>{}, int_c<2>{});
+  if (pos_dim == 3 && nr_feat == 4) return fn(int_c<3>{}, int_c<4>{});
+  return PSDF_ERR_UNSUPPORTED;
+}
+
+// What every entry point hands to every kernel.  Host only: the kernels keep their flat parameter lists; launch_enc (and the
+// two launches of the position kernel, which take Lt as well) unpack it.
+struct EncCall {
+  int64_t N;
+  int nr_levels, Lt, capacity;   // Lt = nr_levels + the pseudo-levels of the concatenated points
+  const float *positions, *lattice, *scale_factor, *shifts, *window;
+  float points_scaling;
+  int pad;
+  hipStream_t stream;
+};
+
+// The argument check every entry point shares (false: PSDF_ERR_ARG), and the bundle.
+bool enc_call(EncCall& c, int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const float* positions,
+              const float* lattice, const float* scale_factor, const float* shifts, const float* window, int concat_points,
+              float points_scaling, void* stream) {
+  if (N < 0 || nr_levels <= 0 || capacity <= 0 || !positions || !lattice || !concat_ok(concat_points)) return false;
+  c = EncCall{N, nr_levels, nr_levels + extra_levels(pos_dim, nr_feat, concat_points), capacity, positions, lattice,
+              scale_factor, shifts, window, points_scaling, pad_points(concat_points), (hipStream_t)stream};
+  return true;
+}
+
+// kern<<<grid, PSDF_BLOCK, shm, stream>>>(N, L, capacity, conventions, positions .. points_scaling, rest...): the head of the
+// parameter list of the forward, backward and double-backward kernels.  (A kernel's default arguments do not apply through a
+// pointer: `rest` names every remaining parameter.)
+template <class Kernel, class... Rest>
+void launch_enc(Kernel kern, dim3 grid, size_t shm, const EncCall& c, Rest... rest) {
+  hipLaunchKernelGGL(kern, grid, dim3(PSDF_BLOCK), shm, c.stream, c.N, c.nr_levels, (uint32_t)c.capacity, psdf::enc_conv_state(),
+                     c.positions, c.lattice, c.scale_factor, c.shifts, c.window, c.points_scaling, rest...);
+}
+
+// what an entry point returns after its launches
+int launched(int rc) {
+  if (rc != PSDF_OK) return rc;
+  PSDF_LAUNCH_CHECK();
+  return PSDF_OK;
+}
+
+int device_cus() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
+// Plain (cache + atomics) mode of the backward and the double backward: a workgroup sets up and flushes a 48-KiB LDS cache, so
+// it should walk several tiles; PSDF_ENC_BWD_WG_PER_LEVEL overrides the per-level workgroup cap (measurement switch).
+dim3 plain_grid(const EncCall& c) {
+  static const int wg_cap_env = env_int("PSDF_ENC_BWD_WG_PER_LEVEL", 0);
+  const unsigned wg_cap = wg_cap_env > 0 ? (unsigned)wg_cap_env : 512u, nb = psdf_blocks(c.N, PSDF_BLOCK);
+  return dim3(nb < wg_cap ? nb : wg_cap, c.Lt);
+}
+
+// ---------------------------------------------------------------------------------- forward
+template <int P, int F>
+int launch_fwd(int_c<P>, int_c<F>, const EncCall& c, dim3 grid, const unsigned char* skip, float* sliced, unsigned char* touched,
+               int touch_shift) {
+  const int touch_blocks = (c.capacity + (1 << touch_shift) - 1) >> touch_shift;
+  // (without a mask and a touched-block map the kernel needs fewer scalar registers: 8 instead of 7 waves per SIMD)
+  if (!skip && !touched)
+    launch_enc(encode_fwd_kernel<P, F, true>, grid, 0, c, c.pad, skip, sliced, touched, touch_shift, touch_blocks);
+  else
+    launch_enc(encode_fwd_kernel<P, F, false>, grid, 0, c, c.pad, skip, sliced, touched, touch_shift, touch_blocks);
+  return PSDF_OK;
+}
+
+int encode_forward_impl(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const float* positions,
+                        const float* lattice, const float* scale_factor, const float* shifts, const float* window,
+                        int concat_points, float points_scaling, const unsigned char* skip, float* sliced, void* stream,
+                        unsigned char* touched = nullptr, int touch_shift = 0) {
+  EncCall c;
+  if (N == 0) return PSDF_OK;
+  if (!enc_call(c, pos_dim, nr_feat, N, nr_levels, capacity, positions, lattice, scale_factor, shifts, window, concat_points,
+                points_scaling, stream) || !sliced)
+    return PSDF_ERR_ARG;
+  if ((int64_t)capacity * nr_feat * 4 > 0xffffffffll) return PSDF_ERR_UNSUPPORTED;   // the kernel's 32-bit offsets inside a level
+  dim3 grid(psdf_blocks(N, PSDF_BLOCK), c.Lt);
+  // one resident round of workgroups per level (8 per CU) that walk the tiles, instead of one workgroup per tile: the level's
+  // constants are fetched once per workgroup.  Round 5, 2 M points x 16 levels, forward bracket of the bench step: 0.650 ms
+  // uncapped, 0.646 with 1024, 0.636 with 2048 or 4096 (profiles/r05_mlp_pair_ab.txt).  PSDF_ENC_FWD_WGS=0: one tile each.
+  static const int fwd_env = env_int("PSDF_ENC_FWD_WGS", -1);
+  const int fwd_wgs = fwd_env >= 0 ? fwd_env : device_cus() * 8;
+  if (fwd_wgs > 0 && (int)grid.x > fwd_wgs) grid.x = fwd_wgs;
+  return launched(dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
+    return launch_fwd(p, f, c, grid, skip, sliced, touched, touch_shift);
+  }));
+}
+
+// ---------------------------------------------------------------------------------- position gradient alone
+// The level-group kernel + the slab reduction when stream-ordered scratch is available (not while a graph is being captured:
+// there the float-atomic form runs), PSDF_ENC_POS_ATOMICS=1 forces the atomic form (A/B).
+template <int P, int F, int POS_LPB>
+void launch_bwd_pos_lpb(const EncCall& c, const float* grad_sliced, const unsigned char* skip, float* grad_positions, bool capturing) {
+  static const bool force_atomics = env_int("PSDF_ENC_POS_ATOMICS", 0) != 0;
+  const int groups = (c.Lt + POS_LPB - 1) / POS_LPB;
   // The slabs are per-stream scratch that is never handed back: capped (PSDF_ENC_POS_SLAB_MAX_MB, default 256 MiB = 1.7 M points
   // at 24 + 2 levels) -- a multi-million-sample render pass takes the float-atomic form (same time, profiles/r04_enc_ab.jsonl:
   // what the slabs buy is run-to-run identical normals, which matters to the training step's curvature term at its 49 K samples)
-  static const size_t slab_cap = (size_t)(getenv("PSDF_ENC_POS_SLAB_MAX_MB") ? atoll(getenv("PSDF_ENC_POS_SLAB_MAX_MB")) : 256) << 20;
-  const size_t slab_bytes = (size_t)groups * N * P_ * sizeof(float);
-  float* slabs = (groups > 1 && !force_atomics && !capturing && slab_bytes <= slab_cap) ? (float*)psdf::stream_scratch(slab_bytes, st) : nullptr;
+  static const size_t slab_cap = (size_t)plan::env_long("PSDF_ENC_POS_SLAB_MAX_MB", 256) << 20;
+  const size_t slab_bytes = (size_t)groups * c.N * P * sizeof(float);
+  const bool use_slabs = groups > 1 && !force_atomics && !capturing && slab_bytes <= slab_cap;
+  float* slabs = use_slabs ? (float*)psdf::stream_scratch(slab_bytes, c.stream) : nullptr;
+  const auto pos_kernel = [&](auto kern, float* out) {
+    hipLaunchKernelGGL(kern, dim3(psdf_blocks(c.N, PSDF_BLOCK), groups), dim3(PSDF_BLOCK), 0, c.stream, c.N, c.nr_levels, c.Lt,
+                       (uint32_t)c.capacity, psdf::enc_conv_state(), c.positions, c.lattice, c.scale_factor, c.shifts, c.window,
+                       c.points_scaling, c.pad, grad_sliced, skip, out);
+  };
   if (slabs) {
-    hipLaunchKernelGGL((encode_bwd_pos_kernel<P_, F_, true, POS_LPB>), dim3(nb, groups), dim3(PSDF_BLOCK), 0, st, N, nr_levels, Lt,
-                       (uint32_t)capacity, psdf::enc_conv_state(), positions, lattice, scale_factor, shifts, window,
-                       points_scaling, pad, grad_sliced, skip, slabs);
-    hipLaunchKernelGGL(encode_bwd_pos_reduce_kernel, dim3(psdf_blocks(N * P_, PSDF_BLOCK)), dim3(PSDF_BLOCK), 0, st, N * P_, P_,
-                       groups, slabs, skip, grad_positions);
+    pos_kernel(encode_bwd_pos_kernel<P, F, true, POS_LPB>, slabs);
+    hipLaunchKernelGGL(encode_bwd_pos_reduce_kernel, dim3(psdf_blocks(c.N * P, PSDF_BLOCK)), dim3(PSDF_BLOCK), 0, c.stream,
+                       c.N * P, P, groups, slabs, skip, grad_positions);
   } else {
-    hipLaunchKernelGGL((encode_bwd_pos_kernel<P_, F_, false, POS_LPB>), dim3(nb, groups), dim3(PSDF_BLOCK), 0, st, N, nr_levels, Lt,
-                       (uint32_t)capacity, psdf::enc_conv_state(), positions, lattice, scale_factor, shifts, window,
-                       points_scaling, pad, grad_sliced, skip, grad_positions);
+    pos_kernel(encode_bwd_pos_kernel<P, F, false, POS_LPB>, grad_positions);
   }
 }
 
-template <int P_, int F_>
-static void launch_bwd_pos(int64_t N, int nr_levels, int Lt, int capacity, const float* positions, const float* lattice,
-                           const float* scale_factor, const float* shifts, const float* window, float points_scaling, int pad,
-                           const float* grad_sliced, const unsigned char* skip, float* grad_positions, hipStream_t st) {
+template <int P, int F>
+int launch_bwd_pos(int_c<P>, int_c<F>, const EncCall& c, const float* grad_sliced, const unsigned char* skip, float* grad_positions) {
   // (the capture state is probed once per launch: while a graph is being captured -- the sphere tracer's -- there is no
   // stream-ordered scratch and the float-atomic form runs, as measured in round 2)
-  const bool capturing = psdf::stream_scratch(16, st) == nullptr;
+  const bool capturing = psdf::stream_scratch(16, c.stream) == nullptr;
   if (capturing)
-    launch_bwd_pos_lpb<P_, F_, 4>(N, nr_levels, Lt, capacity, positions, lattice, scale_factor, shifts, window, points_scaling,
-                                  pad, grad_sliced, skip, grad_positions, st, true);
-  else if (N >= ((int64_t)1 << 17))
-    launch_bwd_pos_lpb<P_, F_, 2>(N, nr_levels, Lt, capacity, positions, lattice, scale_factor, shifts, window, points_scaling,
-                                  pad, grad_sliced, skip, grad_positions, st, false);
+    launch_bwd_pos_lpb<P, F, 4>(c, grad_sliced, skip, grad_positions, true);
+  else if (c.N >= ((int64_t)1 << 17))
+    launch_bwd_pos_lpb<P, F, 2>(c, grad_sliced, skip, grad_positions, false);
   else
-    launch_bwd_pos_lpb<P_, F_, 8>(N, nr_levels, Lt, capacity, positions, lattice, scale_factor, shifts, window, points_scaling,
-                                  pad, grad_sliced, skip, grad_positions, st, false);
+    launch_bwd_pos_lpb<P, F, 8>(c, grad_sliced, skip, grad_positions, false);
+  return PSDF_OK;
 }
 
+// ---------------------------------------------------------------------------------- binned lattice gradient
+// The plan (bytes == 0: the path does not apply) and the queues it lays out in the caller's workspace.
+plan::QueuePlan queue_plan(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity) {
+  static const int64_t min_n = plan::env_long("PSDF_ENC_QUEUE_MIN_N", (int64_t)1 << 13);
+  static const int delta = env_int("PSDF_ENC_QUEUE_SLICE_LOG2_DELTA", 1);   // A/B switch
+  return plan::queue_plan(pos_dim, nr_feat, N, nr_levels, capacity, min_n, delta);
+}
+Queues queue_carve(void* ws, const plan::QueuePlan& p) {
+  char* b = (char*)ws;
+  return Queues{(uint16_t*)b, (float*)(b + p.rows_bytes), (int*)(b + p.rows_bytes + p.vals_bytes), p.cap, p.np, p.shift};
+}
+// false: the plain path runs.  Otherwise Q is carved and its counters (and `also_zeroed` bytes behind them) are zeroed on the stream.
+bool queue_begin(int pos_dim, int nr_feat, const EncCall& c, bool wanted, void* ws, int64_t ws_bytes, size_t also_zeroed, Queues& Q,
+                 hipError_t& e) {
+  const plan::QueuePlan p = (wanted && ws) ? queue_plan(pos_dim, nr_feat, c.N, c.nr_levels, c.capacity) : plan::QueuePlan{};
+  if (p.bytes == 0 || ws_bytes < p.bytes) return false;
+  Q = queue_carve(ws, p);
+  e = hipMemsetAsync(Q.tails, 0, (size_t)c.nr_levels * Q.np * sizeof(int) + also_zeroed, c.stream);
+  return true;
+}
+
+// The deal of one resident round of binning workgroups over the levels (see LevelPlan; the arithmetic is plan::redeal).  State
+// of the previous call per process: the deal it launched with and the host-mapped array its workgroups report their durations
+// into (two arrays, used alternately, entries tagged with the call's generation: a call never reads what an older or an
+// unfinished launch wrote as if it were the previous one's).  PSDF_ENC_BWD_BALANCE=0: equal shares.
+struct EncBalance {
+  int levels = 0, total = 0, kind = 0, bucket = -1;
+  const void* ident = nullptr;   // the lattice the launches belong to (encodings of one shape have different cost profiles)
+  uint32_t gen = 0;
+  uint64_t last_use = 0;
+  std::vector<int> counts;
+  uint32_t* times[2] = {nullptr, nullptr};
+  int device = -1;
+};
+constexpr int BAL_STATES = 16;
+std::mutex g_shares_mu;
+std::vector<int> g_last_shares;
+
+// returns false when the plan cannot be used (equal shares through the rectangular grid then).  kind: 0 backward, 1 double
+// backward.  One state per (lattice, kind, levels, size class of N: quarter octaves, round size) -- a training step alternates between
+// several shapes and its sample count moves a little from step to step --, at most BAL_STATES of them (least recently used
+// one is re-used).
+bool encode_balance(int nr_levels, int64_t N, int total, int64_t super_tiles, LevelPlan& lp, const void* ident, int kind) {
+  static const bool off = env_int("PSDF_ENC_BWD_BALANCE", 1) == 0;
+  static std::mutex mu;
+  static EncBalance states[BAL_STATES];
+  static uint64_t tick = 0;
+  if (!plan::deal_eligible(off, nr_levels, total, N)) return false;
+  std::lock_guard<std::mutex> lock(mu);
+  const int bucket = plan::size_bucket(N);
+  // (the key holds the device as well: an address re-used on another GPU -- or after a free -- must not inherit a deal measured
+  //  elsewhere; ADVICE r5)
+  int device = -1;
+  (void)hipGetDevice(&device);
+  EncBalance* Bp = nullptr;
+  for (auto& st_ : states)
+    if (st_.times[0] && st_.ident == ident && st_.device == device && st_.kind == kind && st_.levels == nr_levels && st_.bucket == bucket &&
+        st_.total == total)
+      Bp = &st_;
+  if (!Bp) {
+    for (auto& st_ : states)
+      if (!Bp || st_.last_use < Bp->last_use) Bp = &st_;
+    if (!Bp->times[0]) {
+      for (int i = 0; i < 2; i++) {
+        void* h = nullptr;
+        if (hipHostMalloc(&h, plan::BAL_MAX_WG * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess || !h) {
+          (void)hipGetLastError();
+          if (i == 1) (void)hipHostFree(Bp->times[0]);
+          Bp->times[0] = Bp->times[1] = nullptr;
+          return false;
+        }
+        Bp->times[i] = (uint32_t*)h;
+      }
+    }
+    memset(Bp->times[0], 0, plan::BAL_MAX_WG * sizeof(uint32_t));     // (a launch of the state's previous owner may still write: its
+    memset(Bp->times[1], 0, plan::BAL_MAX_WG * sizeof(uint32_t));     // entries carry an older generation tag and are ignored)
+    Bp->levels = 0;
+  }
+  EncBalance& B = *Bp;
+  B.last_use = ++tick;
+  if (!B.times[0] || !B.times[1]) return false;
+  const int cap = (int)(super_tiles < total ? super_tiles : total);       // more workgroups than super-tiles of a level: idle ones
+  if (B.levels != nr_levels || (int)B.counts.size() != nr_levels) {
+    B.levels = nr_levels;
+    B.kind = kind;
+    B.ident = ident;
+    B.device = device;
+    B.bucket = bucket;
+    B.total = total;
+    B.counts = plan::first_deal(nr_levels, total);
+  } else {
+    plan::redeal_from_times(B.counts, B.times[B.gen & 1], B.gen, total, cap);
+  }
+  B.gen++;
+  lp.n = nr_levels;
+  lp.gen = B.gen;
+  lp.times = B.times[B.gen & 1];
+  const int at = plan::deal_layout(B.counts, cap, lp.first);
+  std::lock_guard<std::mutex> l2(g_shares_mu);
+  g_last_shares = B.counts;
+  return at <= plan::BAL_MAX_WG;
+}
+
+// One resident round of binning workgroups: every workgroup of the launch resident at once and none left over.  The binning
+// kernel is a long walk per workgroup (LDS cache warm-up, then tens of super-tiles), so a second, partly filled round of
+// workgroups is a tail the size of a whole walk: measured on the bench batch (2 M points; 3 workgroups fit a CU, 768 in all)
+// 16 levels x 48 = 768 workgroups 0.96 ms, x 40 1.09, x 56 1.26 (just over one round), x 96 (two rounds) 1.03, x 128 1.10;
+// 24 levels x 32 best.  (Those figures are from the 3-workgroups-per-CU state of the kernel; 5 fit now -- 80 per level at 16
+// levels -- by the same rule.)
+// Returns the workgroups per level of the rectangular grid (the round shared among c.nr_levels).  deal_levels > 0: the round
+// is dealt over that many levels by their measured cost instead where encode_balance has a deal -- then deal.n = deal_levels
+// and the grid is one-dimensional, deal.first[deal.n] workgroups.  A failed occupancy query: 128 per level, no deal.
+template <class Kernel>
+unsigned resident_round(Kernel kern, size_t shm, const EncCall& c, int deal_levels, int kind, LevelPlan& deal) {
+  int per_cu = 0;
+  const bool known = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PSDF_BLOCK, shm) == hipSuccess && per_cu > 0;
+  if (!known) (void)hipGetLastError();
+  const int resident = known ? per_cu * device_cus() : 0;
+  const int64_t tiles = plan::super_tiles(c.N, PSDF_BLOCK * QUEUE_SPT);
+  deal = LevelPlan{};
+  if (known && deal_levels > 0 && !encode_balance(deal_levels, c.N, resident, tiles, deal, c.lattice, kind)) deal = LevelPlan{};
+  return plan::round_share(resident, c.nr_levels, tiles);
+}
+
+template <int F>
+constexpr size_t binning_shm() { return ScatterCache<F, 4096>::bytes() + Q_LDS_INTS * sizeof(int); }
+
+// The lattice-only binning kernel of the backward (DBL = false: grad_sliced alone) and of the double backward (with
+// dd_positions, grad_grad_sliced and the optional second upstream gradient) over `levels` levels, which are the levels of the
+// deal too (the double backward's include the concatenated-point channels; a training step's coarse-to-fine window leaves
+// levels closed, whose workgroups return at once).  Returns the rectangular share per level (the profile build prints it).
+template <int P, int F, bool DBL>
+unsigned launch_binning(const EncCall& c, int levels, const float* grad_sliced, float* grad_lattice, const Queues& Q,
+                        const float* dd_positions, float* grad_grad_sliced, const float* grad_sliced2) {
+  const auto kern = encode_bwd_kernel<P, F, true, false, true, DBL>;
+  LevelPlan deal;
+  const unsigned gx = resident_round(kern, binning_shm<F>(), c, levels, DBL ? 1 : 0, deal);
+  launch_enc(kern, deal.n ? dim3(deal.first[deal.n]) : dim3(gx, levels), binning_shm<F>(), c, grad_sliced, grad_lattice,
+             (float*)nullptr, Q, dd_positions, grad_grad_sliced, DBL ? c.pad : 0, grad_sliced2, deal);
+  return gx;
+}
+
+// folds every queue into LDS and adds the slices to the gradient
+template <int F>
+int launch_queue_reduce(const EncCall& c, const Queues& Q, float* grad_lattice) {
+  const size_t lds_b = (size_t)(1 << Q.shift) * F * sizeof(float);
+  const hipError_t e =
+      hipFuncSetAttribute((const void*)encode_bwd_reduce_kernel<F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL((encode_bwd_reduce_kernel<F>), dim3(Q.np, c.nr_levels), dim3(1024), lds_b, c.stream, (uint32_t)c.capacity, Q,
+                     grad_lattice);
+  return PSDF_OK;
+}
+
+#if defined(PSDF_ENC_PROFILE)
+void enc_profile_report(const EncCall& c, int pos_dim, const Queues& Q, unsigned gx) {
+  static int calls = 0;
+  if (++calls != 8) return;
+  (void)hipStreamSynchronize(c.stream);
+  int prof[192];
+  (void)hipMemcpy(prof, Q.tails + c.nr_levels * Q.np, sizeof(prof), hipMemcpyDeviceToHost);
+  std::vector<int> tails((size_t)c.nr_levels * Q.np);
+  (void)hipMemcpy(tails.data(), Q.tails, tails.size() * sizeof(int), hipMemcpyDeviceToHost);
+  for (int l = 0; l < c.nr_levels; l++) {
+    long long queued = 0;
+    for (int q = 0; q < Q.np; q++) queued += tails[(size_t)l * Q.np + q];
+    fprintf(stderr, "[enc-profile] level %2d: max %8d ticks, mean %8.0f ticks, cache kept by %d of %u workgroups, queued %lld of %lld "
+            "contributions (%.1f %%)\n", l, prof[l], 64.0 * prof[64 + l] / gx, prof[128 + l], gx, queued,
+            (long long)c.N * (pos_dim + 1), 100.0 * queued / ((double)c.N * (pos_dim + 1)));
+  }
+}
+#endif
+
+// ---------------------------------------------------------------------------------- backward
+bool pos_fused() {   // A/B: the round-3 form, the position gradient from inside the binning kernel
+  static const bool on = env_int("PSDF_ENC_POS_FUSED", 0) != 0;
+  return on;
+}
+
+// Q: the carved queues when the binned path applies, NULL for the plain (cache + atomics) path.
+template <int P, int F>
+int launch_bwd(int_c<P> p, int_c<F> f, const EncCall& c, const float* grad_sliced, float* grad_lattice, float* grad_positions,
+               const Queues* Q) {
+  const float* const no_in = nullptr;
+  float* const no_out = nullptr;
+  constexpr size_t plain_shm = ScatterCache<F, 8192>::bytes() + Q_LDS_INTS * sizeof(int);
+  if (!grad_lattice) return launch_bwd_pos(p, f, c, grad_sliced, nullptr, grad_positions);
+  if (!Q) {
+    if (grad_positions)
+      launch_enc(encode_bwd_kernel<P, F, true, true, false>, plain_grid(c), plain_shm, c, grad_sliced, grad_lattice, grad_positions,
+                 Queues{}, no_in, no_out, 0, no_in, LevelPlan{});
+    else
+      launch_enc(encode_bwd_kernel<P, F, true, false, false>, plain_grid(c), plain_shm, c, grad_sliced, grad_lattice, grad_positions,
+                 Queues{}, no_in, no_out, 0, no_in, LevelPlan{});
+    return PSDF_OK;
+  }
+  [[maybe_unused]] unsigned gx;
+  if (grad_positions && pos_fused()) {
+    const auto kern = encode_bwd_kernel<P, F, true, true, true>;
+    LevelPlan none;
+    gx = resident_round(kern, binning_shm<F>(), c, 0, 0, none);
+    launch_enc(kern, dim3(gx, c.Lt), binning_shm<F>(), c, grad_sliced, grad_lattice, grad_positions, *Q, no_in, no_out, 0, no_in, none);
+  } else {
+    // large batch, both gradients: the binning kernel for the lattice (its own levels only) and the level-group kernel for the
+    // positions -- the fused form adds the position gradient with float atomics from inside the binning kernel: +0.98 ms at
+    // 2 M points x 16 levels against 0.63 ms for the separate kernel (round 4)
+    gx = launch_binning<P, F, false>(c, c.nr_levels, grad_sliced, grad_lattice, *Q, no_in, no_out, no_in);
+    if (grad_positions) launch_bwd_pos(p, f, c, grad_sliced, nullptr, grad_positions);
+  }
+  const int rc = launch_queue_reduce<F>(c, *Q, grad_lattice);
+#if defined(PSDF_ENC_PROFILE)
+  if (rc == PSDF_OK) enc_profile_report(c, P, *Q, gx);
+#endif
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------- double backward
+template <int P, int F>
+int launch_dbl_queue(int_c<P>, int_c<F>, const EncCall& c, const float* dd_positions, const float* grad_sliced, float* grad_lattice,
+                     float* grad_grad_sliced, const float* grad_sliced_direct, const Queues& Q) {
+  launch_binning<P, F, true>(c, c.Lt, grad_sliced, grad_lattice, Q, dd_positions, grad_grad_sliced, grad_sliced_direct);
+  return launch_queue_reduce<F>(c, Q, grad_lattice);
+}
+
+template <int P, int F>
+int launch_dbl_plain(int_c<P>, int_c<F>, const EncCall& c, const float* dd_positions, const float* grad_sliced, float* grad_lattice,
+                     float* grad_grad_sliced) {
+  if (grad_lattice)
+    launch_enc(encode_dbl_bwd_kernel<P, F, true>, plain_grid(c), ScatterCache<F>::bytes(), c, c.pad, dd_positions, grad_sliced,
+               grad_lattice, grad_grad_sliced);
+  else
+    launch_enc(encode_dbl_bwd_kernel<P, F, false>, plain_grid(c), 0, c, c.pad, dd_positions, grad_sliced, grad_lattice,
+               grad_grad_sliced);
+  return PSDF_OK;
+}
+
+}  // namespace
+
+// ================================================================================== C ABI
 extern "C" {
 
 // The conventions in force, by index: 0 hash multiplier, 1 rank tie rule (both RUNTIME values: the defaults of
@@ -1132,50 +1478,6 @@ int psdf_encode_set_conventions(uint32_t hash_multiplier, int rank_tie_raises_la
   return PSDF_OK;
 }
 
-static int device_cus();
-static int encode_forward_impl(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const float* positions,
-                               const float* lattice, const float* scale_factor, const float* shifts, const float* window,
-                               int concat_points, float points_scaling, const unsigned char* skip, float* sliced,
-                               void* stream, unsigned char* touched = nullptr, int touch_shift = 0) {
-  if (N == 0) return PSDF_OK;
-  if (N < 0 || nr_levels <= 0 || capacity <= 0 || !positions || !lattice || !sliced || !concat_ok(concat_points))
-    return PSDF_ERR_ARG;
-  if ((int64_t)capacity * nr_feat * 4 > 0xffffffffll) return PSDF_ERR_UNSUPPORTED;   // the kernel's 32-bit offsets inside a level
-  hipStream_t st = (hipStream_t)stream;
-  const int Lt = nr_levels + extra_levels(pos_dim, nr_feat, concat_points);
-  dim3 grid(psdf_blocks(N, PSDF_BLOCK), Lt);
-  // one resident round of workgroups per level (8 per CU) that walk the tiles, instead of one workgroup per tile: the level's
-  // constants are fetched once per workgroup.  Round 5, 2 M points x 16 levels, forward bracket of the bench step: 0.650 ms
-  // uncapped, 0.646 with 1024, 0.636 with 2048 or 4096 (profiles/r05_mlp_pair_ab.txt).  PSDF_ENC_FWD_WGS=0: one tile each.
-  static const int fwd_env = getenv("PSDF_ENC_FWD_WGS") ? atoi(getenv("PSDF_ENC_FWD_WGS")) : -1;
-  const int fwd_wgs = fwd_env >= 0 ? fwd_env : device_cus() * 8;
-  if (fwd_wgs > 0 && (int)grid.x > fwd_wgs) grid.x = fwd_wgs;
-#define FWD_(P_, F_, PL_)                                                                                      \
-  hipLaunchKernelGGL((encode_fwd_kernel<P_, F_, PL_>), grid, dim3(PSDF_BLOCK), 0, st, N, nr_levels, (uint32_t)capacity, psdf::enc_conv_state(), \
-                     positions, lattice, scale_factor, shifts, window, points_scaling, pad_points(concat_points), skip, sliced,  \
-                     touched, touch_shift, (capacity + (1 << touch_shift) - 1) >> touch_shift)
-  // (without a mask and a touched-block map the kernel needs fewer scalar registers: 8 instead of 7 waves per SIMD)
-#define FWD(P_, F_)                          \
-  do {                                       \
-    if (!skip && !touched) FWD_(P_, F_, true); \
-    else FWD_(P_, F_, false);                \
-  } while (0)
-  if (pos_dim == 3 && nr_feat == 2)
-    FWD(3, 2);
-  else if (pos_dim == 4 && nr_feat == 2)
-    FWD(4, 2);
-  else if (pos_dim == 2 && nr_feat == 2)
-    FWD(2, 2);
-  else if (pos_dim == 3 && nr_feat == 4)
-    FWD(3, 4);
-  else
-    return PSDF_ERR_UNSUPPORTED;
-#undef FWD
-#undef FWD_
-  PSDF_LAUNCH_CHECK();
-  return PSDF_OK;
-}
-
 int psdf_encode_forward(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const float* positions,
                         const float* lattice, const float* scale_factor, const float* shifts, const float* window,
                         int concat_points, float points_scaling, float* sliced, void* stream) {
@@ -1193,49 +1495,6 @@ int psdf_encode_forward_masked(int pos_dim, int nr_feat, int64_t N, int nr_level
                              concat_points, points_scaling, skip, sliced, stream);
 }
 
-// Workspace for the binned (queue + LDS reduction) lattice-gradient path; 0 = the path does not apply (small batch,
-// table too large for 64 partitions) and psdf_encode_backward_ws behaves exactly like psdf_encode_backward.
-static bool queue_plan(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, Queues& Q, int64_t& bytes) {
-  bytes = 0;
-  // Below ~8 K points the fixed cost of the plan (counter memset, one resident round of binning workgroups, a reduce pass over
-  // the whole table: ~27 us for 24 levels x 2^18 rows) exceeds what the plain path (LDS cache + float atomics, ~4.7 ns per point
-  // when every level carries a gradient) spends.  Measured, tools/small_batch_enc_bench.py, lattice backward: 1 056 points
-  // 10.8 us plain / 27.1 us queued; 49 152 points 232 / 71.5 us; 262 080 points 1206 / 174.5 us.  (Until round 3 the
-  // threshold was 2^18 points: every backward of a training step -- ~49 K ray samples -- took the plain path.)
-  static const int64_t min_n = getenv("PSDF_ENC_QUEUE_MIN_N") ? atoll(getenv("PSDF_ENC_QUEUE_MIN_N")) : ((int64_t)1 << 13);
-  if (N < min_n) return false;
-  // rows per partition: the reduce kernel holds a partition's slice of the table in LDS.  64-KiB slices (two reduce
-  // workgroups per CU) instead of the 128 KiB that fit: the coarse levels' queues are nearly empty, so with one workgroup per
-  // (level, partition) and 16 partitions only half the CUs had work (16 levels: reduce + binning 0.966 -> 0.905 ms with 32).
-  const int base = (nr_feat <= 2) ? 14 : (nr_feat <= 4 ? 13 : 12);   // rows/partition * F * 4 B <= 128 KiB
-  static const int delta = getenv("PSDF_ENC_QUEUE_SLICE_LOG2_DELTA") ? atoi(getenv("PSDF_ENC_QUEUE_SLICE_LOG2_DELTA")) : 1;   // A/B switch
-  int shift = base - (delta < 0 ? 0 : (delta > 3 ? 3 : delta));
-  while (shift < base && ((capacity + (1 << shift) - 1) >> shift) > Q_MAX_PARTS) shift++;   // large tables: keep the partition count
-  const int rpp = 1 << shift;
-  const int np = (capacity + rpp - 1) / rpp;
-  if (np > Q_MAX_PARTS || rpp * nr_feat * 4 > 128 * 1024) return false;
-  const int64_t contrib = (int64_t)(pos_dim + 1) * N;
-  const int64_t cap = (contrib / np) + (contrib / np) / 4 + 4096;
-  if (cap > 0x7fffffff) return false;
-  // the kernels address a level's slice of the queues with 32-bit byte offsets (queue_store)
-  if ((int64_t)np * cap * (nr_feat * 4 > 2 ? nr_feat * 4 : 2) > 0xffffffffll) return false;
-  Q.cap = (int)cap;
-  Q.np = np;
-  Q.shift = shift;
-  const int64_t entries = (int64_t)nr_levels * np * cap;
-  const int64_t rows_b = (entries * 2 + 255) & ~(int64_t)255, vals_b = (entries * nr_feat * 4 + 255) & ~(int64_t)255;
-  bytes = rows_b + vals_b + (((int64_t)nr_levels * np * 4 + 255) & ~(int64_t)255) + 1024;   // + profile slots (variant builds)
-  return true;
-}
-static void queue_carve(void* ws, int nr_feat, int nr_levels, Queues& Q) {
-  const int64_t entries = (int64_t)nr_levels * Q.np * Q.cap;
-  const int64_t rows_b = (entries * 2 + 255) & ~(int64_t)255, vals_b = (entries * nr_feat * 4 + 255) & ~(int64_t)255;
-  char* p = (char*)ws;
-  Q.rows = (uint16_t*)p;
-  Q.vals = (float*)(p + rows_b);
-  Q.tails = (int*)(p + rows_b + vals_b);
-}
-
 // Forward that also records the blocks of 2^block_rows_log2 table rows it reads: touched_blocks [nr_levels, ceil(capacity /
 // 2^block_rows_log2)] bytes, set to 1 (never cleared here).  See psdf_adamw_step_blocks.
 int psdf_encode_forward_mark(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const float* positions,
@@ -1247,171 +1506,11 @@ int psdf_encode_forward_mark(int pos_dim, int nr_feat, int64_t N, int nr_levels,
                              concat_points, points_scaling, nullptr, sliced, stream, touched_blocks, block_rows_log2);
 }
 
+// Workspace for the binned (queue + LDS reduction) lattice-gradient path; 0 = the path does not apply (small batch,
+// table too large for 64 partitions) and psdf_encode_backward_ws behaves exactly like psdf_encode_backward.  Host only.
 int64_t psdf_encode_backward_workspace_bytes(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity) {
-  Queues Q{};
-  int64_t bytes = 0;
-  queue_plan(pos_dim, nr_feat, N, nr_levels, capacity, Q, bytes);
-  return bytes;
+  return queue_plan(pos_dim, nr_feat, N, nr_levels, capacity).bytes;
 }
-
-// grad_lattice / grad_positions must be zero-initialised by the caller (or hold a running sum to add to);
-// either may be NULL to skip that gradient.  workspace: device scratch of at least
-// psdf_encode_backward_workspace_bytes() bytes (contents undefined on entry and exit) or NULL.
-static int device_cus() {
-  static int cus[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n;
-  }
-  return cus[dev];
-}
-
-}  // extern "C"
-
-// The deal of one resident round of binning workgroups over the levels (see LevelPlan).  State of the previous call per process:
-// the plan it launched with and the host-mapped array its workgroups report their durations into (two arrays, used alternately,
-// entries tagged with the call's generation: a call never reads what an older or an unfinished launch wrote as if it were the
-// previous one's).  share_l <- 1/2 share_l + 1/2 (count_l x mean duration_l) / sum: a level whose workgroups ran longer gets
-// more of them next time; a closed level (its workgroups return at once) falls to the minimum.  PSDF_ENC_BWD_BALANCE=0: equal shares.
-namespace {
-struct EncBalance {
-  int levels = 0, total = 0, kind = 0, bucket = -1;
-  const void* ident = nullptr;   // the lattice the launches belong to (encodings of one shape have different cost profiles)
-  uint32_t gen = 0;
-  uint64_t last_use = 0;
-  std::vector<int> counts;
-  uint32_t* times[2] = {nullptr, nullptr};
-  int device = -1;
-};
-constexpr int BAL_MAX_WG = 8192, BAL_MIN_PER_LEVEL = 4, BAL_STATES = 16;
-std::mutex g_shares_mu;
-std::vector<int> g_last_shares;
-
-// returns false when the plan cannot be used (equal shares through the rectangular grid then).  kind: 0 backward, 1 double
-// backward.  One state per (lattice, kind, levels, size class of N: quarter octaves, round size) -- a training step alternates between
-// several shapes and its sample count moves a little from step to step --, at most BAL_STATES of them (least recently used
-// one is re-used).
-bool encode_balance(int nr_levels, int64_t N, int total, int64_t super_tiles, LevelPlan& plan, const void* ident, int kind = 0) {
-  static const bool off = getenv("PSDF_ENC_BWD_BALANCE") && atoi(getenv("PSDF_ENC_BWD_BALANCE")) == 0;
-  static std::mutex mu;
-  static EncBalance states[BAL_STATES];
-  static uint64_t tick = 0;
-  // (batches below 2^18 points: a training step's 49 152 samples have fewer super-tiles per level than a level's equal share of
-  // the round, and the measured effect is inside the run-to-run noise, 449 / 447 it/s with against 471 / 438 without: off)
-  if (off || nr_levels > 40 || total > BAL_MAX_WG || total < nr_levels * BAL_MIN_PER_LEVEL || N < ((int64_t)1 << 18)) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  int bucket = 0;
-  for (int64_t v = N; v > 1; v >>= 1) bucket += 4;
-  {
-    const int64_t top = (int64_t)1 << (bucket / 4);
-    bucket += (int)(((N - top) * 4) / top);
-  }
-  // (the key holds the device as well: an address re-used on another GPU -- or after a free -- must not inherit a deal measured
-  //  elsewhere; ADVICE r5)
-  int device = -1;
-  (void)hipGetDevice(&device);
-  EncBalance* Bp = nullptr;
-  for (auto& st_ : states)
-    if (st_.times[0] && st_.ident == ident && st_.device == device && st_.kind == kind && st_.levels == nr_levels && st_.bucket == bucket &&
-        st_.total == total)
-      Bp = &st_;
-  if (!Bp) {
-    for (auto& st_ : states)
-      if (!Bp || st_.last_use < Bp->last_use) Bp = &st_;
-    if (!Bp->times[0]) {
-      for (int i = 0; i < 2; i++) {
-        void* h = nullptr;
-        if (hipHostMalloc(&h, BAL_MAX_WG * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess || !h) {
-          (void)hipGetLastError();
-          if (i == 1) (void)hipHostFree(Bp->times[0]);
-          Bp->times[0] = Bp->times[1] = nullptr;
-          return false;
-        }
-        Bp->times[i] = (uint32_t*)h;
-      }
-    }
-    memset(Bp->times[0], 0, BAL_MAX_WG * sizeof(uint32_t));     // (a launch of the state's previous owner may still write: its
-    memset(Bp->times[1], 0, BAL_MAX_WG * sizeof(uint32_t));     // entries carry an older generation tag and are ignored)
-    Bp->levels = 0;
-  }
-  EncBalance& B = *Bp;
-  B.last_use = ++tick;
-  if (!B.times[0] || !B.times[1]) return false;
-  const int cap = (int)(super_tiles < total ? super_tiles : total);       // more workgroups than super-tiles of a level: idle ones
-  if (B.levels != nr_levels || (int)B.counts.size() != nr_levels) {
-    B.levels = nr_levels;
-    B.kind = kind;
-    B.ident = ident;
-    B.device = device;
-    B.bucket = bucket;
-    B.total = total;
-    B.counts.assign(nr_levels, total / nr_levels);
-  } else {
-    // what the previous call's workgroups reported (all of them, with its tag -- otherwise the launch is still running, or
-    // another shape ran in between: keep the deal)
-    const volatile uint32_t* t = B.times[B.gen & 1];
-    std::vector<double> work(nr_levels, 0.0);
-    bool complete = true;
-    int id = 0;
-    double sum = 0.0;
-    for (int l = 0; l < nr_levels && complete; l++) {
-      double acc = 0.0;
-      for (int b = 0; b < B.counts[l]; b++, id++) {
-        const uint32_t v = t[id];
-        if ((v >> 24) != (B.gen & 255u) || (v & 0xFFFFFFu) == 0u) {
-          complete = false;
-          break;
-        }
-        acc += (double)(v & 0xFFFFFFu);
-      }
-      work[l] = acc;       // = count x mean duration
-      sum += acc;
-    }
-    if (complete && sum > 0.0) {
-      std::vector<double> want(nr_levels);
-      for (int l = 0; l < nr_levels; l++) want[l] = 0.5 * B.counts[l] + 0.5 * total * work[l] / sum;
-      int used = 0;
-      for (int l = 0; l < nr_levels; l++) {
-        int c = (int)(want[l] + 0.5);
-        c = c < BAL_MIN_PER_LEVEL ? BAL_MIN_PER_LEVEL : (c > cap ? cap : c);
-        B.counts[l] = c;
-        used += c;
-      }
-      // never more than one resident round: take the excess from the largest shares
-      while (used > total) {
-        int big = 0;
-        for (int l = 1; l < nr_levels; l++)
-          if (B.counts[l] > B.counts[big]) big = l;
-        if (B.counts[big] <= BAL_MIN_PER_LEVEL) break;
-        B.counts[big]--;
-        used--;
-      }
-    }
-  }
-  B.gen++;
-  plan.n = nr_levels;
-  plan.gen = B.gen;
-  plan.times = B.times[B.gen & 1];
-  int at = 0;
-  for (int l = 0; l < nr_levels; l++) {
-    if (B.counts[l] > cap) B.counts[l] = cap;
-    if (B.counts[l] < 1) B.counts[l] = 1;
-    plan.first[l] = (uint16_t)at;
-    at += B.counts[l];
-  }
-  plan.first[nr_levels] = (uint16_t)at;
-  {
-    std::lock_guard<std::mutex> l2(g_shares_mu);
-    g_last_shares = B.counts;
-  }
-  return at <= BAL_MAX_WG;
-}
-}  // namespace
-
-extern "C" {
 
 // the deal of the last balanced launch (debug query): counts[0 .. nr_levels), returns nr_levels (0: none yet)
 int psdf_encode_backward_level_shares(int* counts, int max_levels) {
@@ -1421,143 +1520,33 @@ int psdf_encode_backward_level_shares(int* counts, int max_levels) {
   return n;
 }
 
+// grad_lattice / grad_positions must be zero-initialised by the caller (or hold a running sum to add to);
+// either may be NULL to skip that gradient.  workspace: device scratch of at least
+// psdf_encode_backward_workspace_bytes() bytes (contents undefined on entry and exit) or NULL.
 int psdf_encode_backward_ws(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const float* positions,
                             const float* lattice, const float* scale_factor, const float* shifts, const float* window,
                             int concat_points, float points_scaling, const float* grad_sliced, float* grad_lattice,
                             float* grad_positions, void* workspace, int64_t workspace_bytes, void* stream) {
+  EncCall c;
   if (N == 0 || (!grad_lattice && !grad_positions)) return PSDF_OK;
-  if (N < 0 || nr_levels <= 0 || capacity <= 0 || !positions || !lattice || !grad_sliced || !concat_ok(concat_points))
+  if (!enc_call(c, pos_dim, nr_feat, N, nr_levels, capacity, positions, lattice, scale_factor, shifts, window, concat_points,
+                points_scaling, stream) || !grad_sliced)
     return PSDF_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int Lt = nr_levels + ((grad_positions != nullptr) ? extra_levels(pos_dim, nr_feat, concat_points) : 0);
-  const unsigned nb = psdf_blocks(N, PSDF_BLOCK);
-  // Plain (cache + atomics) mode: a workgroup sets up and flushes a 48-KiB LDS cache, so it should walk several tiles;
-  // PSDF_ENC_BWD_WG_PER_LEVEL overrides the per-level workgroup cap (measurement switch).
-  static const int wg_cap_env = getenv("PSDF_ENC_BWD_WG_PER_LEVEL") ? atoi(getenv("PSDF_ENC_BWD_WG_PER_LEVEL")) : 0;
-  const unsigned wg_cap = wg_cap_env > 0 ? (unsigned)wg_cap_env : 512u;
-  dim3 grid(nb < wg_cap ? nb : wg_cap, Lt);
-  static const bool pos_fused = getenv("PSDF_ENC_POS_FUSED") && atoi(getenv("PSDF_ENC_POS_FUSED")) != 0;   // A/B: the round-3 form
+  if (!grad_positions) c.Lt = nr_levels;   // the pseudo-levels of the concatenated points carry a position gradient only
   Queues Q{};
-  int64_t need = 0;
-  const bool use_queue = grad_lattice && workspace && queue_plan(pos_dim, nr_feat, N, nr_levels, capacity, Q, need) &&
-                         workspace_bytes >= need;
-  if (use_queue) {
-    grid.x = 128;  // provisional: BWD_PF sizes it to ONE resident round of workgroups (see there)
-    queue_carve(workspace, nr_feat, nr_levels, Q);
+  hipError_t e = hipSuccess;
 #if defined(PSDF_ENC_PROFILE)
-    hipError_t e = hipMemsetAsync(Q.tails, 0, (size_t)nr_levels * Q.np * sizeof(int) + 1024, st);
+  const size_t profile_slots = 1024;
 #else
-    hipError_t e = hipMemsetAsync(Q.tails, 0, (size_t)nr_levels * Q.np * sizeof(int), st);
+  const size_t profile_slots = 0;
 #endif
-    if (e != hipSuccess) return (int)e;
-  }
-#define BWD(P_, F_, A_, B_, Q_)                                                                                  \
-  hipLaunchKernelGGL((encode_bwd_kernel<P_, F_, A_, B_, Q_>), grid, dim3(PSDF_BLOCK),                             \
-                     ((A_) ? ScatterCache<F_, ((Q_) ? 4096 : 8192)>::bytes() + Q_LDS_INTS * sizeof(int) : 0), st, N, \
-                     nr_levels,                                                                                    \
-                     (uint32_t)capacity, psdf::enc_conv_state(), positions, lattice, scale_factor, shifts, window, points_scaling,        \
-                     grad_sliced, grad_lattice, grad_positions, Q)
-// Queue mode: every workgroup of the launch resident at once and none left over.  The binning kernel is a long walk per
-// workgroup (LDS cache warm-up, then tens of super-tiles), so a second, partly filled round of workgroups is a tail the
-// size of a whole walk: measured on the bench batch (2 M points; 3 workgroups fit a CU, 768 in all) 16 levels x 48 = 768
-// workgroups 0.96 ms, x 40 1.09, x 56 1.26 (just over one round), x 96 (two rounds) 1.03, x 128 1.10; 24 levels x 32 best.
-// (Those figures are from the 3-workgroups-per-CU state of the kernel; 5 fit now -- 80 per level at 16 levels -- by the same rule.)
-#define BWD_PLAN(P_, F_)                                                                                          \
-  hipLaunchKernelGGL((encode_bwd_kernel<P_, F_, true, false, true>), dim3(plan.first[nr_levels]), dim3(PSDF_BLOCK), \
-                     (ScatterCache<F_, 4096>::bytes() + Q_LDS_INTS * sizeof(int)), st, N, nr_levels,    \
-                     (uint32_t)capacity, psdf::enc_conv_state(), positions, lattice, scale_factor, shifts, window, \
-                     points_scaling, grad_sliced, grad_lattice, (float*)nullptr, Q, (const float*)nullptr,          \
-                     (float*)nullptr, 0, (const float*)nullptr, plan)
-#define BWD_PF(P_, F_)                                                                                           \
-  do {                                                                                                           \
-    LevelPlan plan{};                                                                                            \
-    bool balanced = false;                                                                                       \
-    if (use_queue) {                                                                                             \
-      int per_cu = 0;                                                                                            \
-      const size_t shm = ScatterCache<F_, 4096>::bytes() + Q_LDS_INTS * sizeof(int);                  \
-      const hipError_t eo =                                                                                      \
-          (grad_positions && pos_fused) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(                                        \
-                               &per_cu, encode_bwd_kernel<P_, F_, true, true, true>, PSDF_BLOCK, shm)            \
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(                                        \
-                               &per_cu, encode_bwd_kernel<P_, F_, true, false, true>, PSDF_BLOCK, shm);          \
-      if (eo == hipSuccess && per_cu > 0) {                                                                      \
-        int64_t gx = (int64_t)per_cu * device_cus() / nr_levels;                                                 \
-        const int64_t super_tiles = (N + (int64_t)PSDF_BLOCK * QUEUE_SPT - 1) / ((int64_t)PSDF_BLOCK * QUEUE_SPT); \
-        if (gx > super_tiles) gx = super_tiles;                                                                  \
-        grid.x = (unsigned)(gx < 1 ? 1 : gx);                                                                    \
-        /* lattice-only binning launches: the round is dealt over the levels by their measured cost */           \
-        if (!(grad_positions && pos_fused))                                                                      \
-          balanced = encode_balance(nr_levels, N, per_cu * device_cus(), super_tiles, plan, lattice);                     \
-      } else {                                                                                                   \
-        (void)hipGetLastError();                                                                                 \
-      }                                                                                                          \
-    }                                                                                                            \
-    if (use_queue && grad_positions && !pos_fused) {                                                             \
-      /* large batch, both gradients: the binning kernel for the lattice (its own levels only) and the level-group */ \
-      /* kernel for the positions -- the fused form adds the position gradient with float atomics from inside the */ \
-      /* binning kernel: +0.98 ms at 2 M points x 16 levels against 0.63 ms for the separate kernel (round 4) */   \
-      grid.y = nr_levels;                                                                                        \
-      if (balanced) BWD_PLAN(P_, F_); else BWD(P_, F_, true, false, true);                                       \
-      launch_bwd_pos<P_, F_>(N, nr_levels, Lt, capacity, positions, lattice, scale_factor, shifts, window,        \
-                             points_scaling, pad_points(concat_points), grad_sliced, (const unsigned char*)nullptr, \
-                             grad_positions, st);                                                                 \
-    } else if (use_queue && grad_positions)                                                                      \
-      BWD(P_, F_, true, true, true);                                                                             \
-    else if (use_queue) {                                                                                        \
-      if (balanced) BWD_PLAN(P_, F_); else BWD(P_, F_, true, false, true);                                       \
-    }                                                                                                            \
-    else if (grad_lattice && grad_positions)                                                                     \
-      BWD(P_, F_, true, true, false);                                                                            \
-    else if (grad_lattice)                                                                                       \
-      BWD(P_, F_, true, false, false);                                                                           \
-    else                                                                                                         \
-      launch_bwd_pos<P_, F_>(N, nr_levels, Lt, capacity, positions, lattice, scale_factor, shifts, window,        \
-                             points_scaling, pad_points(concat_points), grad_sliced, (const unsigned char*)nullptr, \
-                             grad_positions, st);                                                                 \
-    if (use_queue) {                                                                                             \
-      const size_t lds_b = (size_t)(1 << Q.shift) * F_ * sizeof(float);                                          \
-      hipError_t e2 = hipFuncSetAttribute((const void*)encode_bwd_reduce_kernel<F_>,                              \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);                \
-      if (e2 != hipSuccess) return (int)e2;                                                                      \
-      hipLaunchKernelGGL((encode_bwd_reduce_kernel<F_>), dim3(Q.np, nr_levels), dim3(1024), lds_b, st,            \
-                         (uint32_t)capacity, Q, grad_lattice);                                                   \
-    }                                                                                                            \
-  } while (0)
-  if (pos_dim == 3 && nr_feat == 2)
-    BWD_PF(3, 2);
-  else if (pos_dim == 4 && nr_feat == 2)
-    BWD_PF(4, 2);
-  else if (pos_dim == 2 && nr_feat == 2)
-    BWD_PF(2, 2);
-  else if (pos_dim == 3 && nr_feat == 4)
-    BWD_PF(3, 4);
-  else
-    return PSDF_ERR_UNSUPPORTED;
-#undef BWD_PF
-#undef BWD_PLAN
-#undef BWD
-  psdf::g_last_path[psdf::PATH_ENCODE_BWD] = use_queue ? 2 : (grad_lattice ? 1 : 3);
-#if defined(PSDF_ENC_PROFILE)
-  if (use_queue) {
-    static int calls = 0;
-    if (++calls == 8) {
-      (void)hipStreamSynchronize(st);
-      int prof[192];
-      (void)hipMemcpy(prof, Q.tails + nr_levels * Q.np, sizeof(prof), hipMemcpyDeviceToHost);
-      std::vector<int> tails((size_t)nr_levels * Q.np);
-      (void)hipMemcpy(tails.data(), Q.tails, tails.size() * sizeof(int), hipMemcpyDeviceToHost);
-      for (int l = 0; l < nr_levels; l++) {
-        long long queued = 0;
-        for (int q = 0; q < Q.np; q++) queued += tails[(size_t)l * Q.np + q];
-        fprintf(stderr, "[enc-profile] level %2d: max %8d ticks, mean %8.0f ticks, cache kept by %d of %u workgroups, queued %lld of %lld "
-                "contributions (%.1f %%)\n", l, prof[l], 64.0 * prof[64 + l] / grid.x, prof[128 + l], grid.x, queued,
-                (long long)N * (pos_dim + 1), 100.0 * queued / ((double)N * (pos_dim + 1)));
-      }
-    }
-  }
-#endif
-  PSDF_LAUNCH_CHECK();
-  return PSDF_OK;
+  const bool use_queue = queue_begin(pos_dim, nr_feat, c, grad_lattice, workspace, workspace_bytes, profile_slots, Q, e);
+  if (e != hipSuccess) return (int)e;
+  const int rc = dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
+    return launch_bwd(p, f, c, grad_sliced, grad_lattice, grad_positions, use_queue ? &Q : nullptr);
+  });
+  if (rc == PSDF_OK) psdf::g_last_path[psdf::PATH_ENCODE_BWD] = use_queue ? 2 : (grad_lattice ? 1 : 3);
+  return launched(rc);
 }
 
 int psdf_encode_backward(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const float* positions,
@@ -1576,28 +1565,14 @@ int psdf_encode_backward_positions_masked(int pos_dim, int nr_feat, int64_t N, i
                                           const float* shifts, const float* window, int concat_points, float points_scaling,
                                           const float* grad_sliced, const unsigned char* skip, float* grad_positions,
                                           void* stream) {
+  EncCall c;
   if (N == 0) return PSDF_OK;
-  if (N < 0 || nr_levels <= 0 || capacity <= 0 || !positions || !lattice || !grad_sliced || !grad_positions ||
-      !concat_ok(concat_points))
+  if (!enc_call(c, pos_dim, nr_feat, N, nr_levels, capacity, positions, lattice, scale_factor, shifts, window, concat_points,
+                points_scaling, stream) || !grad_sliced || !grad_positions)
     return PSDF_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int Lt = nr_levels + extra_levels(pos_dim, nr_feat, concat_points);
-#define POS(P_, F_)                                                                                                  \
-  launch_bwd_pos<P_, F_>(N, nr_levels, Lt, capacity, positions, lattice, scale_factor, shifts, window, points_scaling, \
-                         pad_points(concat_points), grad_sliced, skip, grad_positions, st)
-  if (pos_dim == 3 && nr_feat == 2)
-    POS(3, 2);
-  else if (pos_dim == 4 && nr_feat == 2)
-    POS(4, 2);
-  else if (pos_dim == 2 && nr_feat == 2)
-    POS(2, 2);
-  else if (pos_dim == 3 && nr_feat == 4)
-    POS(3, 4);
-  else
-    return PSDF_ERR_UNSUPPORTED;
-#undef POS
-  PSDF_LAUNCH_CHECK();
-  return PSDF_OK;
+  return launched(dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
+    return launch_bwd_pos(p, f, c, grad_sliced, skip, grad_positions);
+  }));
 }
 
 // grad_lattice must be zero-initialised (or NULL to skip); grad_grad_sliced is fully overwritten.  workspace: device scratch of
@@ -1610,63 +1585,19 @@ int psdf_encode_double_backward_ws(int pos_dim, int nr_feat, int64_t N, int nr_l
                                    const float* dd_positions, const float* grad_sliced, float* grad_lattice,
                                    float* grad_grad_sliced, const float* grad_sliced_direct, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
+  EncCall c;
   if (N == 0) return PSDF_OK;
-  if (N < 0 || nr_levels <= 0 || capacity <= 0 || !positions || !lattice || !dd_positions || !grad_sliced ||
-      (!grad_grad_sliced && !grad_lattice) || (grad_sliced_direct && !grad_lattice) || !concat_ok(concat_points))
+  if (!enc_call(c, pos_dim, nr_feat, N, nr_levels, capacity, positions, lattice, scale_factor, shifts, window, concat_points,
+                points_scaling, stream) || !dd_positions || !grad_sliced || (!grad_grad_sliced && !grad_lattice) ||
+      (grad_sliced_direct && !grad_lattice))
     return PSDF_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int Lt = nr_levels + extra_levels(pos_dim, nr_feat, concat_points);
-  const unsigned nb = psdf_blocks(N, PSDF_BLOCK);
-  {
-    Queues Q{};
-    int64_t need = 0;
-    if (grad_lattice && workspace && queue_plan(pos_dim, nr_feat, N, nr_levels, capacity, Q, need) && workspace_bytes >= need) {
-      queue_carve(workspace, nr_feat, nr_levels, Q);
-      hipError_t e = hipMemsetAsync(Q.tails, 0, (size_t)nr_levels * Q.np * sizeof(int), st);
-      if (e != hipSuccess) return (int)e;
-#define DBLQ(P_, F_)                                                                                                     \
-  do {                                                                                                                   \
-    auto kern = encode_bwd_kernel<P_, F_, true, false, true, true>;                                                      \
-    const size_t shm = ScatterCache<F_, 4096>::bytes() + Q_LDS_INTS * sizeof(int);                            \
-    int per_cu = 0;                                                                                                      \
-    int64_t gx = 128;                                                                                                    \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PSDF_BLOCK, shm) == hipSuccess && per_cu > 0)        \
-      gx = (int64_t)per_cu * device_cus() / nr_levels;   /* one resident round, as in psdf_encode_backward_ws */         \
-    else                                                                                                                 \
-      (void)hipGetLastError();                                                                                           \
-    const int64_t super_tiles = (N + (int64_t)PSDF_BLOCK * QUEUE_SPT - 1) / ((int64_t)PSDF_BLOCK * QUEUE_SPT);           \
-    if (gx > super_tiles) gx = super_tiles;                                                                              \
-    /* the round dealt over the levels by their measured cost (the concatenated-point channels are levels of the deal): */ \
-    /* a training step's coarse-to-fine window leaves levels closed, whose workgroups return at once */                   \
-    LevelPlan plan{};                                                                                                    \
-    dim3 g2((unsigned)(gx < 1 ? 1 : gx), Lt);                                                                            \
-    if (per_cu > 0 && encode_balance(Lt, N, per_cu * device_cus(), super_tiles, plan, lattice, 1)) g2 = dim3(plan.first[Lt]);       \
-    else plan = LevelPlan{};                                                                                             \
-    hipLaunchKernelGGL(kern, g2, dim3(PSDF_BLOCK), shm, st, N, nr_levels,                                                \
-                       (uint32_t)capacity, psdf::enc_conv_state(), positions, lattice, scale_factor, shifts, window,     \
-                       points_scaling, grad_sliced, grad_lattice, (float*)nullptr, Q, dd_positions, grad_grad_sliced,    \
-                       pad_points(concat_points), grad_sliced_direct, plan);                                             \
-    const size_t lds_b = (size_t)(1 << Q.shift) * F_ * sizeof(float);                                                    \
-    hipError_t e2 = hipFuncSetAttribute((const void*)encode_bwd_reduce_kernel<F_>,                                       \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);                         \
-    if (e2 != hipSuccess) return (int)e2;                                                                                \
-    hipLaunchKernelGGL((encode_bwd_reduce_kernel<F_>), dim3(Q.np, nr_levels), dim3(1024), lds_b, st, (uint32_t)capacity, \
-                       Q, grad_lattice);                                                                                 \
-  } while (0)
-      if (pos_dim == 3 && nr_feat == 2)
-        DBLQ(3, 2);
-      else if (pos_dim == 4 && nr_feat == 2)
-        DBLQ(4, 2);
-      else if (pos_dim == 2 && nr_feat == 2)
-        DBLQ(2, 2);
-      else if (pos_dim == 3 && nr_feat == 4)
-        DBLQ(3, 4);
-      else
-        return PSDF_ERR_UNSUPPORTED;
-#undef DBLQ
-      PSDF_LAUNCH_CHECK();
-      return PSDF_OK;
-    }
+  Queues Q{};
+  hipError_t e = hipSuccess;
+  if (queue_begin(pos_dim, nr_feat, c, grad_lattice, workspace, workspace_bytes, 0, Q, e)) {
+    if (e != hipSuccess) return (int)e;
+    return launched(dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
+      return launch_dbl_queue(p, f, c, dd_positions, grad_sliced, grad_lattice, grad_grad_sliced, grad_sliced_direct, Q);
+    }));
   }
   // small batches: the plain double-backward kernel (it always writes the gathered output: give it scratch when the caller
   // wants the lattice gradient only), and the direct part as an ordinary backward
@@ -1677,39 +1608,12 @@ int psdf_encode_double_backward_ws(int pos_dim, int nr_feat, int64_t N, int nr_l
     if (rc != PSDF_OK) return rc;
   }
   if (!grad_grad_sliced) {
-    grad_grad_sliced = (float*)psdf::stream_scratch((size_t)Lt * nr_feat * N * sizeof(float), st);
+    grad_grad_sliced = (float*)psdf::stream_scratch((size_t)c.Lt * nr_feat * N * sizeof(float), c.stream);
     if (!grad_grad_sliced) return PSDF_ERR_UNSUPPORTED;
   }
-  // Plain (cache + atomics) mode: a workgroup sets up and flushes a 48-KiB LDS cache, so it should walk several tiles;
-  // PSDF_ENC_BWD_WG_PER_LEVEL overrides the per-level workgroup cap (measurement switch).
-  static const int wg_cap_env = getenv("PSDF_ENC_BWD_WG_PER_LEVEL") ? atoi(getenv("PSDF_ENC_BWD_WG_PER_LEVEL")) : 0;
-  const unsigned wg_cap = wg_cap_env > 0 ? (unsigned)wg_cap_env : 512u;
-  dim3 grid(nb < wg_cap ? nb : wg_cap, Lt);
-#define DBL(P_, F_)                                                                                              \
-  do {                                                                                                           \
-    if (grad_lattice)                                                                                            \
-      hipLaunchKernelGGL((encode_dbl_bwd_kernel<P_, F_, true>), grid, dim3(PSDF_BLOCK), ScatterCache<F_>::bytes(), \
-                         st, N, nr_levels, (uint32_t)capacity, psdf::enc_conv_state(), positions, lattice, scale_factor, shifts, window,   \
-                         points_scaling, pad_points(concat_points), dd_positions, grad_sliced, grad_lattice,       \
-                         grad_grad_sliced);                                                                        \
-    else                                                                                                         \
-      hipLaunchKernelGGL((encode_dbl_bwd_kernel<P_, F_, false>), grid, dim3(PSDF_BLOCK), 0, st, N, nr_levels,      \
-                         (uint32_t)capacity, psdf::enc_conv_state(), positions, lattice, scale_factor, shifts, window, points_scaling,     \
-                         pad_points(concat_points), dd_positions, grad_sliced, grad_lattice, grad_grad_sliced);    \
-  } while (0)
-  if (pos_dim == 3 && nr_feat == 2)
-    DBL(3, 2);
-  else if (pos_dim == 4 && nr_feat == 2)
-    DBL(4, 2);
-  else if (pos_dim == 2 && nr_feat == 2)
-    DBL(2, 2);
-  else if (pos_dim == 3 && nr_feat == 4)
-    DBL(3, 4);
-  else
-    return PSDF_ERR_UNSUPPORTED;
-#undef DBL
-  PSDF_LAUNCH_CHECK();
-  return PSDF_OK;
+  return launched(dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
+    return launch_dbl_plain(p, f, c, dd_positions, grad_sliced, grad_lattice, grad_grad_sliced);
+  }));
 }
 
 int psdf_encode_double_backward(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity,

@@ -1,0 +1,145 @@
+// encode_plan.h -- the host arithmetic behind the launches of encode.hip, in one place: the plan of the binned (queue + LDS
+// reduction) lattice-gradient path, the size of one resident round of its workgroups, and the deal of that round over the
+// levels.  Integers and doubles only: no HIP, no device, no state -- a plain C++17 compiler accepts this header, and
+// tests/host/encode_plan_check.cpp runs it under the address and undefined-behaviour sanitizers.  What needs a device, a lock
+// or memory that outlives a call (occupancy query, host-mapped arrays, the states of encode_balance) stays in encode.hip.
+#pragma once
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+namespace psdf {
+namespace enc_plan {
+
+// Environment switches: an integer or the default.  Callers keep the value in a function-local static (read once per process).
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+inline long long env_long(const char* name, long long dflt) { const char* v = getenv(name); return v ? atoll(v) : dflt; }
+
+// ------------------------------------------------------------------------------------------ queue plan
+constexpr int Q_MAX_PARTS = 64;   // partitions of a level's table (the binning kernel keeps four counters per partition in LDS)
+
+// bytes == 0: the path does not apply (small batch, table too large for Q_MAX_PARTS partitions, queues past the kernels' 32-bit
+// offsets) and every other field is 0.  The workspace is [rows | vals | tails | 1024 B of profile slots (variant builds)].
+struct QueuePlan {
+  int cap, np, shift;   // entries per (level, partition) queue; partitions; rows per partition = 1 << shift
+  int64_t rows_bytes, vals_bytes, tails_bytes, bytes;
+};
+
+// min_n: PSDF_ENC_QUEUE_MIN_N (default 2^13); slice_delta: PSDF_ENC_QUEUE_SLICE_LOG2_DELTA (default 1, A/B switch).
+inline QueuePlan queue_plan(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, int64_t min_n, int slice_delta) {
+  // Below ~8 K points the fixed cost of the plan (counter memset, one resident round of binning workgroups, a reduce pass over
+  // the whole table: ~27 us for 24 levels x 2^18 rows) exceeds what the plain path (LDS cache + float atomics, ~4.7 ns per point
+  // when every level carries a gradient) spends.  Measured, tools/small_batch_enc_bench.py, lattice backward: 1 056 points
+  // 10.8 us plain / 27.1 us queued; 49 152 points 232 / 71.5 us; 262 080 points 1206 / 174.5 us.  (Until round 3 the
+  // threshold was 2^18 points: every backward of a training step -- ~49 K ray samples -- took the plain path.)
+  if (N < min_n) return QueuePlan{};
+  // rows per partition: the reduce kernel holds a partition's slice of the table in LDS.  64-KiB slices (two reduce
+  // workgroups per CU) instead of the 128 KiB that fit: the coarse levels' queues are nearly empty, so with one workgroup per
+  // (level, partition) and 16 partitions only half the CUs had work (16 levels: reduce + binning 0.966 -> 0.905 ms with 32).
+  const int base = (nr_feat <= 2) ? 14 : (nr_feat <= 4 ? 13 : 12);   // rows/partition * F * 4 B <= 128 KiB
+  int shift = base - (slice_delta < 0 ? 0 : (slice_delta > 3 ? 3 : slice_delta));
+  while (shift < base && ((capacity + (1 << shift) - 1) >> shift) > Q_MAX_PARTS) shift++;   // large tables: keep the partition count
+  const int rpp = 1 << shift;
+  const int np = (capacity + rpp - 1) / rpp;
+  if (np > Q_MAX_PARTS || rpp * nr_feat * 4 > 128 * 1024) return QueuePlan{};
+  const int64_t contrib = (int64_t)(pos_dim + 1) * N;
+  const int64_t cap = (contrib / np) + (contrib / np) / 4 + 4096;
+  if (cap > 0x7fffffff) return QueuePlan{};
+  // the kernels address a level's slice of the queues with 32-bit byte offsets (queue_store)
+  if ((int64_t)np * cap * (nr_feat * 4 > 2 ? nr_feat * 4 : 2) > 0xffffffffll) return QueuePlan{};
+  const auto round256 = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+  const int64_t entries = (int64_t)nr_levels * np * cap;
+  QueuePlan p{(int)cap, np, shift, round256(entries * 2), round256(entries * nr_feat * 4), round256((int64_t)nr_levels * np * 4), 0};
+  p.bytes = p.rows_bytes + p.vals_bytes + p.tails_bytes + 1024;
+  return p;
+}
+
+// ------------------------------------------------------------------------------------------ one resident round
+// The binning kernel walks super-tiles of `tile` points (block size x points per thread).
+inline int64_t super_tiles(int64_t N, int tile) { return (N + tile - 1) / tile; }
+
+// Workgroups per level of a rectangular grid: `resident` (workgroups per CU x CUs) shared among nr_levels, never more than a
+// level has super-tiles, at least 1.  resident <= 0 (the occupancy query failed): 128 per level under the same clamp.
+inline unsigned round_share(int resident, int nr_levels, int64_t tiles) {
+  int64_t gx = resident > 0 ? (int64_t)resident / nr_levels : 128;
+  if (gx > tiles) gx = tiles;
+  return (unsigned)(gx < 1 ? 1 : gx);
+}
+
+// ------------------------------------------------------------------------------------------ the level deal
+// share_l <- 1/2 share_l + 1/2 total x work_l / sum(work): a level whose workgroups ran longer gets more of the round next time;
+// a closed level (its workgroups return at once) falls to the minimum.
+constexpr int BAL_MAX_WG = 8192, BAL_MIN_PER_LEVEL = 4, BAL_MAX_LEVELS = 40;
+
+// Size class of N: quarter octaves.
+inline int size_bucket(int64_t N) {
+  int bucket = 0;
+  for (int64_t v = N; v > 1; v >>= 1) bucket += 4;
+  const int64_t top = (int64_t)1 << (bucket / 4);
+  return bucket + (int)(((N - top) * 4) / top);
+}
+
+// (batches below 2^18 points: a training step's 49 152 samples have fewer super-tiles per level than a level's equal share of
+// the round, and the measured effect is inside the run-to-run noise, 449 / 447 it/s with against 471 / 438 without: off)
+inline bool deal_eligible(bool switched_off, int nr_levels, int total, int64_t N) {
+  return !(switched_off || nr_levels > BAL_MAX_LEVELS || total > BAL_MAX_WG || total < nr_levels * BAL_MIN_PER_LEVEL ||
+           N < ((int64_t)1 << 18));
+}
+
+inline std::vector<int> first_deal(int nr_levels, int total) { return std::vector<int>((size_t)nr_levels, total / nr_levels); }
+
+// work[l] = count_l x mean duration_l.  cap: no level gets more workgroups than it has super-tiles (idle ones).
+inline void redeal(std::vector<int>& counts, const double* work, int total, int cap) {
+  const int n = (int)counts.size();
+  double sum = 0.0;
+  for (int l = 0; l < n; l++) sum += work[l];
+  if (!(sum > 0.0)) return;
+  int used = 0;
+  for (int l = 0; l < n; l++) {
+    int c = (int)(0.5 * counts[l] + 0.5 * total * work[l] / sum + 0.5);
+    c = c < BAL_MIN_PER_LEVEL ? BAL_MIN_PER_LEVEL : (c > cap ? cap : c);
+    counts[l] = c;
+    used += c;
+  }
+  // never more than one resident round: take the excess from the largest shares
+  while (used > total) {
+    int big = 0;
+    for (int l = 1; l < n; l++)
+      if (counts[l] > counts[big]) big = l;
+    if (counts[big] <= BAL_MIN_PER_LEVEL) break;
+    counts[big]--;
+    used--;
+  }
+}
+
+// What the previous launch's workgroups reported into times[] (one entry each, in level order: 24-bit duration, tagged with the
+// low 8 bits of the launch's generation).  All of them, with that tag: re-deal; otherwise the launch is still running, or
+// another shape ran in between: keep the deal (returns false).
+inline bool redeal_from_times(std::vector<int>& counts, const volatile uint32_t* times, uint32_t gen, int total, int cap) {
+  std::vector<double> work(counts.size(), 0.0);
+  int id = 0;
+  for (size_t l = 0; l < counts.size(); l++)
+    for (int b = 0; b < counts[l]; b++, id++) {
+      const uint32_t v = times[id];
+      if ((v >> 24) != (gen & 255u) || (v & 0xFFFFFFu) == 0u) return false;
+      work[l] += (double)(v & 0xFFFFFFu);
+    }
+  redeal(counts, work.data(), total, cap);
+  return true;
+}
+
+// Final clamp to [1, cap] and the prefix layout: workgroups [first[l], first[l + 1]) serve level l.  Returns the grid size.
+inline int deal_layout(std::vector<int>& counts, int cap, uint16_t* first) {
+  int at = 0;
+  for (size_t l = 0; l < counts.size(); l++) {
+    if (counts[l] > cap) counts[l] = cap;
+    if (counts[l] < 1) counts[l] = 1;
+    first[l] = (uint16_t)at;
+    at += counts[l];
+  }
+  first[counts.size()] = (uint16_t)at;
+  return at;
+}
+
+}  // namespace enc_plan
+}  // namespace psdf

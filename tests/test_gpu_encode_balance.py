@@ -1,5 +1,6 @@
 """GPU: the binning launch of the large-batch encode backward deals its resident round of workgroups over the levels by their
-measured cost (csrc/encode.hip, LevelPlan / encode_balance).  The deal changes nothing but the schedule: the gradient equals
+measured cost (csrc/encode.hip: LevelPlan, resident_round, encode_balance; the arithmetic of the deal is csrc/encode_plan.h, checked
+without a GPU by tests/test_encode_host_plan.py).  The deal changes nothing but the schedule: the gradient equals
 the equal-share launch's up to the order of float additions, and closed levels fall to the minimum share."""
 import ctypes
 

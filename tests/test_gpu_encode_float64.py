@@ -13,7 +13,8 @@ that one lost contribution is far above it.  The worst error / bar of each compa
 
 Paths are asserted through psdf_last_path(0) where the library reports one (1 plain lattice kernel, 2 queue + reduce, 3
 position kernel alone); the queue-full fallback is proved from the tail counters of a workspace the test supplies itself
-(`queue_plan` below mirrors the host function of the same name and is pinned to psdf_encode_backward_workspace_bytes).
+(`queue_plan` below is an independent restatement of queue_plan() in csrc/encode_plan.h, pinned to
+psdf_encode_backward_workspace_bytes here and, on the CPU, to a recorded grid by tests/test_encode_host_plan.py).
 
 Cases the library cannot be asked to confirm from outside (written here so that nobody assumes more): which of the slab / float-
 atomic forms of the position kernel ran (decided by size and capture state inside launch_bwd_pos: the sizes below are chosen
@@ -63,7 +64,7 @@ def workspace_bytes(s, N):
 
 
 def queue_plan(P, F, N, L, T):
-    """mirror of queue_plan() in csrc/encode.hip (default environment): None = the plain path runs"""
+    """mirror of queue_plan() in csrc/encode_plan.h (default environment): None = the plain path runs"""
     if N < (1 << 13):
         return None
     base = 14 if F <= 2 else 13

@@ -1,6 +1,6 @@
 """GPU: ORACLE PARITY OF THE CONFIGURATION THAT IS TIMED.  bench.py times SdfHotPath.step at 2 097 152 samples, where the
 library dispatches to `mlp_fwd_split_kernel`, `mlp_bwd_split_kernel` (N >= 2^18, csrc/mlp_bwd.hip) and the queue-mode encode
-backward `encode_bwd_kernel<..,queue>` + `encode_bwd_reduce_kernel` (N >= 2^18, csrc/encode.hip queue_plan).  These tests run
+backward `encode_bwd_kernel<..,queue>` + `encode_bwd_reduce_kernel` (N >= 2^18, queue_plan of csrc/encode_plan.h).  These tests run
 that dispatch -- asserted through psdf_last_path(), not assumed -- against the CPU oracle chain (oracle/hotpath_oracle.py:
 oracle/permuto_oracle.py + unmodified torch.nn + oracle/neus_oracle.py, torch autograd):
 
