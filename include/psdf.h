@@ -574,6 +574,62 @@ int psdf_mesh_grid_points(int nx, int Y, int Z, int x0, int64_t first, int64_t c
 int psdf_mesh_sparse_mask(int64_t count, int nr_voxels_per_dim, float extent, const float* grid_translation, const uint8_t*
     grid_occupancy, const float* points, float h, uint8_t* valid, uint8_t* skip, void* stream);
 
+/* ---- mesh_eval.hip ---- */
+/* The DTU Chamfer protocol the reference scores its meshes with (permuto_sdf_py/experiments/evaluation/
+   evaluate_chamfer_distance.py calls permuto_sdf_py/experiments/evaluation/DTUeval-python/eval.py) on device tensors.  The
+   entries allocate nothing and never synchronise; sorts and scans are the caller's; an empty batch returns 0 before any
+   pointer check.  The uniform grid of a cloud is (origin_edge [4] = lower corner and cell edge, dims [3]), host arrays, from
+   psdf_mesh_eval_grid_plan (csrc/mesh_eval_plan.h). */
+/* reference points per LDS tile of psdf_mesh_nn_cooperative (host only) */
+int psdf_mesh_eval_tile_capacity(void);
+/* host only: the grid of n_points points with bounding box [lo, hi] (3 doubles each; the finite points' fp32 extremes), a cell
+   edge >= min_edge (the caller's search radius, 0: none) and at most cell_budget cells (<= 0: the default) -> origin_edge [4],
+   dims [3], *cells = dims[0] dims[1] dims[2] (int64), *query_blocks (optional) = blocks of 4 x 4 x 4 cells.  -1: bad box / count;
+   -2: more than 2^31 - 1 points */
+int psdf_mesh_eval_grid_plan(const double* lo, const double* hi, int64_t n_points, double min_edge, int64_t cell_budget, float*
+    origin_edge, int* dims, int64_t* cells, int64_t* query_blocks);
+/* replaces: the lattice sampling of every triangle, eval.py:9-18 (sample_single_tri) and :53-69 (edge vectors, the spacing
+   thr = density sqrt(l1 l2 / area2), n = floor(l / thr), one pool task per triangle).  V [nV, 3] fp32, F [nF, 3] int32;
+   counts [nF] int32 <- samples of every triangle: decisions in float64 from the fp32 corners, (i + 1/2) / max(n, 1e-7) and the
+   strict a + b < 1 as written there; a triangle of zero area counts 0.  *overflow (int32, zeroed by the caller) |= 1 when a
+   triangle has more than 30 000 lattice steps on an edge, |= 2 when a face names a vertex outside [0, nV): both count 0. */
+int psdf_mesh_sample_count(const float* V, int64_t nV, const int32_t* F, int64_t nF, double density, int32_t* counts, int32_t*
+    overflow, void* stream);
+/* incl [nF] int64 = the caller's INCLUSIVE scan of counts; samples [incl[nF - 1], 3] fp32 <- p0 + a e1 + b e2 evaluated in
+   float64 and rounded once, triangle by triangle, i-major, j-minor (the order of eval.py:67-69) */
+int psdf_mesh_sample_emit(const float* V, int64_t nV, const int32_t* F, int64_t nF, double density, const int64_t* incl, float*
+    samples, void* stream);
+/* keys [n] int32 <- the cell of every point (block_log2 = 0: (cx ny + cy) nz + cz) or its block of (1 << block_log2)^3 cells
+   (numbered the same way over the blocks); cx = (int)clamp((p - origin) / edge, 0, n - 1) with the clamp in fp32: the one cell
+   function of this file.  A point with a non-finite coordinate gets the number of cells (blocks): the key past every cell. */
+int psdf_mesh_eval_cell_keys(const float* points, int64_t n, const float* origin_edge, const int* dims, int block_log2, int32_t*
+    keys, void* stream);
+/* start [cells + 1] int32 <- first position of sorted_keys [n] (ascending: the caller's sort) with a key >= c: cell c owns
+   [start[c], start[c + 1]) and start[cells] = number of finite points.  n = 0 is a valid call (all zero). */
+int psdf_mesh_eval_cell_ranges(const int32_t* sorted_keys, int64_t n, int64_t cells, int32_t* start, void* stream);
+/* replaces: the radius_neighbors query and the sequential kill loop of eval.py:85-93 (after the shuffle of :80-81) by sweeps of
+   the parallel form of the same set (the lexicographically first maximal independent set of the d <= radius graph under the
+   order `rank`).  points [n, 3] / rank [n] / keys [n] in CELL-SORTED order, cell_start from psdf_mesh_eval_cell_ranges of a
+   grid with edge >= radius (1 + 1/512) (-1 otherwise); state [n] bytes, zeroed by the caller before the first sweep: 0
+   undecided, 1 kept, 2 dropped.  One call = one in-place sweep; *undecided (int32, zeroed by the caller before every sweep) +=
+   points still undecided after it.  The caller sweeps until it reads 0; d = sqrtf of the fp32 difference form. */
+int psdf_mesh_thin_sweep(const float* points, const int32_t* rank, const int32_t* keys, int64_t n, const int32_t* cell_start,
+    const float* origin_edge, const int* dims, float radius, uint8_t* state, int32_t* undecided, void* stream);
+/* replaces: the KD-tree kneighbors queries of eval.py:118-121 and :131-133 (data -> scan, scan -> data, distances below
+   max_dist averaged).  refs [nr, 3] sorted by cell with cell_start; queries [nq, 3] sorted by block of 4 x 4 x 4 cells of THE
+   SAME grid (psdf_mesh_eval_cell_keys with block_log2 = 2) with query_block_start [blocks + 1].  One workgroup per block stages
+   the references of the block and its one-cell halo through LDS tiles and every lane tests its query: dist [nq] / idx [nq]
+   (position in the SORTED references) <- nearest reference strictly closer than max_dist, else (max_dist, -1); open [nq] <- 1
+   where that is not yet proven (best > distance to the boundary of the cells searched); *nr_open (int32, zeroed by the caller)
+   += their number.  Queries outside every block (non-finite ones) are not written: the caller pre-fills (max_dist, -1, 0). */
+int psdf_mesh_nn_cooperative(const float* queries, int64_t nq, const int32_t* query_block_start, const float* refs, int64_t nr,
+    const int32_t* cell_start, const float* origin_edge, const int* dims, float max_dist, float* dist, int32_t* idx, uint8_t*
+    open, int32_t* nr_open, void* stream);
+/* finishes the queries with open != 0: shells of cells around the query's own cell, from shell 2 on, until best <= distance to
+   the boundary of the shells searched (best starts at max_dist: never further than the cut-off) */
+int psdf_mesh_nn_ring(const float* queries, int64_t nq, const float* refs, int64_t nr, const int32_t* cell_start, const float*
+    origin_edge, const int* dims, float max_dist, float* dist, int32_t* idx, const uint8_t* open, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
