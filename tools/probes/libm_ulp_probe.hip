@@ -1,6 +1,7 @@
-// Worst observed error, in fp32 ulps of the float64 result, of the device expf / log1pf / __expf over the argument ranges the
-// compositing kernels use (csrc/neus.hip, composite_device.h, csrc/volume_rendering.hip).  The figures feed ULP_EXPF,
-// ULP_LOG1PF and ULP_FAST_EXPF of oracle/composite_float64.py (worst observed, rounded up to a whole ulp, plus one).
+// Worst observed error, in fp32 ulps of the float64 result, of the device expf / log1pf / __expf / acosf over the argument
+// ranges the compositing kernels and the loss tails use (csrc/neus.hip, composite_device.h, csrc/volume_rendering.hip).  The
+// figures feed ULP_EXPF, ULP_LOG1PF and ULP_FAST_EXPF of oracle/composite_float64.py and ULP_ACOSF of oracle/tails_float64.py
+// (worst observed, rounded up to a whole ulp, plus one).
 //   hipcc -O3 -ffp-contract=off --offload-arch=gfx950 tools/probes/libm_ulp_probe.hip -o tools/probes/libm_ulp_probe
 // Every fp32 value of each range is visited when the range holds fewer than 2^26 of them, else 2^26 evenly spaced bit patterns.
 #include <hip/hip_runtime.h>
@@ -11,7 +12,7 @@
 #include <cstring>
 
 __device__ __forceinline__ float fn(int which, float x) {
-  return which == 0 ? expf(x) : which == 1 ? log1pf(x) : __expf(x);
+  return which == 0 ? expf(x) : which == 1 ? log1pf(x) : which == 2 ? __expf(x) : acosf(x);
 }
 
 __global__ void eval(int which, uint32_t lo_bits, uint32_t step, uint32_t count, float* out) {
@@ -53,7 +54,7 @@ static void run(const char* name, int which, float a, float b) {
   float worst_x = 0.f;
   for (uint32_t i = 0; i < count; i++) {
     const float x = bits(lo + i * step);
-    const double ref = which == 1 ? log1p((double)x) : exp((double)x);
+    const double ref = which == 1 ? log1p((double)x) : which == 3 ? acos((double)x) : exp((double)x);
     if (!(ref >= 1.1754943508222875e-38) || !(ref < 3.4e38)) continue;   // normal results only: below that the bar is absolute
     int e;
     frexp(ref, &e);
@@ -80,5 +81,8 @@ int main() {
   // __expf(-sigma dt) of volume_render_nerf: the early-out at T < 1e-4 keeps the products that matter above -20
   run("__expf", 2, -1e-8f, -20.0f);
   run("__expf", 2, -20.0f, -87.3f);
+  // acosf(clamp(n(a) . n(b), -1 + 1e-6, 1 - 1e-6)) of curvature_loss_kernel: the fp32 clamp edges are the last arguments
+  run("acosf", 3, 1e-30f, 1.0f - 1e-6f);
+  run("acosf", 3, -1e-30f, -1.0f + 1e-6f);
   return 0;
 }
