@@ -97,6 +97,14 @@ int psdf_mlp_pack_f16(int n_layers, const int* dims, const float* const* weights
     void* stream);
 int psdf_mlp_forward_f16(int n_layers, const int* dims, int64_t N, const float* X, const float* packed, float* Y, void* stream);
 
+/* Test and A/B hook of the split forward kernels (psdf_mlp_forward, _masked and _f16 where they take the split-operand kernel):
+   psdf_mlp_forward_set_form forces the workgroup form, `waves` per workgroup sharing one weight image (4, 8 or 16; 0 = the
+   launch policy picks by batch size again; -1 for any other value), for the process until it is called again.  A forward whose
+   net has no kernel of the forced form returns -2 and launches nothing.  psdf_mlp_forward_last_form: the waves per workgroup of
+   the last split forward launch (0: none yet); psdf_last_path(2) keeps naming the arithmetic.  No reference counterpart. */
+int psdf_mlp_forward_set_form(int waves);
+int psdf_mlp_forward_last_form(void);
+
 /* ---- composite_fused.hip ---- */
 /* replaces, fused: VolumeRenderingNeus.compute_weights + integrate (permuto_sdf_py/volume_rendering/volume_rendering_modules.py:
    129-190), i.e. the chain psdf_neus_alpha_forward -> psdf_cumprod_alpha2transmittance -> (alpha * T) ->

@@ -223,15 +223,16 @@ __global__ void __launch_bounds__(PSDF_BLOCK, 2)
     if constexpr (F16) apply_gelu_packed<T_>(H_); \
     else apply_gelu_scalar<T_>(H_);               \
   } while (0)
-template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16 = false>
-__global__ void __launch_bounds__(PSDF_BLOCK, 2)
-    mlp_fwd_split_kernel(MlpPlan p, SplitPlan sp, int64_t N, const float* __restrict__ X,
-                         const float* __restrict__ packed, const unsigned char* __restrict__ skip,
-                         float* __restrict__ Y) {
+// W: waves of the workgroup, which share ONE weight image (the image, not the registers, is what limits the residency of the
+// 64-wide nets: see SPLIT_LDS_MAX in mlp_device.h).  Wave w of workgroup b walks the tiles b W + w, + gridDim.x W, ...
+template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16, int W>
+__device__ __forceinline__ void mlp_fwd_split_body(const MlpPlan& p, const SplitPlan& sp, int64_t N, const float* __restrict__ X,
+                                                   const float* __restrict__ packed, const unsigned char* __restrict__ skip,
+                                                   float* __restrict__ Y) {
   extern __shared__ __align__(16) u32x4 simg[];
   {
     const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(packed + sp.base);
-    for (int i = threadIdx.x; i < sp.total_rec; i += PSDF_BLOCK) simg[i] = src[i];
+    for (int i = threadIdx.x; i < sp.total_rec; i += W * 64) simg[i] = src[i];
   }
   __syncthreads();
   const float* tail = reinterpret_cast<const float*>(simg + sp.tail_rec);
@@ -241,7 +242,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK, 2)
   const int OUT = p.dims[p.n_layers];
   const int ns0 = sp.ns[0];
   const int64_t ntiles = (N + 31) / 32;
-  for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
+  for (int64_t tile = (int64_t)blockIdx.x * W + wave; tile < ntiles; tile += (int64_t)gridDim.x * W) {
     asm volatile("" ::: "memory");  // keeps the loop-invariant LDS reads inside the tile loop (see mlp_fwd_kernel)
     const int64_t n = tile * 32 + sl;
     const int64_t nc = n < N ? n : N - 1;
@@ -323,22 +324,128 @@ __global__ void __launch_bounds__(PSDF_BLOCK, 2)
   }
 }
 
+// The four-wave form: every net of the SPLIT column, every batch size.
 template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16 = false>
-int launch_fwd_split_ch(const MlpPlan& p, const SplitPlan& sp, int64_t N, const float* X, const float* packed,
-                     const unsigned char* skip, float* Y, hipStream_t st) {
+__global__ void __launch_bounds__(PSDF_BLOCK, 2)
+    mlp_fwd_split_kernel(MlpPlan p, SplitPlan sp, int64_t N, const float* __restrict__ X,
+                         const float* __restrict__ packed, const unsigned char* __restrict__ skip,
+                         float* __restrict__ Y) {
+  mlp_fwd_split_body<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16, 4>(p, sp, N, X, packed, skip, Y);
+}
+
+// The wide form: W waves on one image, four waves per SIMD (128 registers each: 512 per SIMD lane over four waves) -- W = 8 is
+// two workgroups per CU, W = 16 one.  Built for the 64-wide nets only, and for one W (split_wide_built below).
+template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16, int W>
+__global__ void __launch_bounds__(W * 64, 4)
+    mlp_fwd_split_wg_kernel(MlpPlan p, SplitPlan sp, int64_t N, const float* __restrict__ X,
+                            const float* __restrict__ packed, const unsigned char* __restrict__ skip,
+                            float* __restrict__ Y) {
+  mlp_fwd_split_body<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16, W>(p, sp, N, X, packed, skip, Y);
+}
+
+// ---- which workgroup form a launch takes
+// The wide form that is built.  W = 8 and W = 16 tie at the bench size (0.2580 / 0.2583 ms, profiles/mlp_fwd_forms_ab.txt); 8 is
+// kept because it also holds between the powers of two (24 tiles per CU: 29 us against 36 us; two workgroups per CU overlap
+// one's staging and tail with the other's tiles).
+constexpr int SPLIT_WIDE_W = 8;
+constexpr int SPLIT_WIDE_MIN_TILES_PER_CU = 16;   // the launch policy's threshold, see launch_fwd_split_ch
+
+// The wide form exists where the weight image is what limits the residency and the kernel fits 128 registers without scratch:
+// the 64-wide rows of PSDF_MLP32_ROWS with one output tile, <2, 2, 2, 1, true> (both piece forms) and <2, 2, 0, 1, true>.  The
+// 32-wide rows have 20 KB images and up to 161 registers; they keep the four-wave form.
+template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int W>
+constexpr bool split_wide_built = T1 == 2 && T2 == 2 && (T3 == 2 || T3 == 0) && OUT_T == 1 && FINAL_DOT && W == SPLIT_WIDE_W;
+
+int g_fwd_form_forced = 0;   // psdf_mlp_forward_set_form: 0 = by the launch policy
+int g_fwd_form_last = 0;     // waves per workgroup of the last split forward launch
+
+int mlp_device_cus() {
+  static int cus[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
+// one launch of one form; the grid is ONE resident round (occupancy x CUs, asked once per kernel, device and image size), so the image
+// is staged once per resident workgroup and every wave walks tiles for the rest of the launch
+template <int W, auto KERN>
+int launch_fwd_split_form(const MlpPlan& p, const SplitPlan& sp, int64_t N, const float* X, const float* packed,
+                          const unsigned char* skip, float* Y, hipStream_t st) {
+  const auto kern = KERN;
   const size_t shmem = (size_t)sp.total_rec * 16;
-  auto kern = mlp_fwd_split_kernel<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16>;
-  if (shmem > 64 * 1024) {
+  if (shmem > 64 * 1024) {   // on every launch: the attribute belongs to the current device's copy of the kernel
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return (int)e;
   }
+  // workgroups per CU of THIS kernel (statics of the instantiation), per device and image size.  Host state like g_last_path:
+  // not synchronised, one thread launches at a time.
+  struct Round { size_t shmem; int per_cu; };
+  static Round rounds[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  Round& r = rounds[dev];
+  if (r.shmem != shmem || r.per_cu <= 0) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, W * 64, shmem) != hipSuccess || per_cu <= 0) {
+      (void)hipGetLastError();
+      per_cu = 2;        // what 160 KB of LDS allow a 64-wide net's image, in either form
+    }
+    r = Round{shmem, per_cu};
+  }
+  const int round_per_cu = r.per_cu;
   const int64_t ntiles = (N + 31) / 32;
-  int64_t blocks = (ntiles + 3) / 4;
-  const int64_t cap = 256 * 4;
+  int64_t blocks = (ntiles + W - 1) / W;
+  const int64_t cap = (int64_t)round_per_cu * mlp_device_cus();
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(PSDF_BLOCK), shmem, st, p, sp, N, X, packed, skip, Y);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W * 64), shmem, st, p, sp, N, X, packed, skip, Y);
   PSDF_LAUNCH_CHECK();
+  g_fwd_form_last = W;
   return PSDF_OK;
+}
+
+// the wide form of W waves where it is built; -2 (and no launch) where it is not: a forced form this net does not have
+template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16, int W>
+int launch_fwd_split_wide(const MlpPlan& p, const SplitPlan& sp, int64_t N, const float* X, const float* packed,
+                          const unsigned char* skip, float* Y, hipStream_t st) {
+  if constexpr (split_wide_built<T1, T2, T3, OUT_T, FINAL_DOT, W>)
+    return launch_fwd_split_form<W, mlp_fwd_split_wg_kernel<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16, W>>(p, sp, N, X, packed, skip, Y,
+                                                                                                         st);
+  else
+    return PSDF_ERR_UNSUPPORTED;
+}
+
+// Launch policy.  The wide form is taken when every CU gets a full resident round of it, 16 tiles (two 8-wave workgroups);
+// below that the four-wave form spreads a small batch (a training step's 49 K samples: 1536 tiles) over all CUs.  Measured on
+// MI355X (256 CUs), us per launch, median of 15, forced forms (profiles/mlp_fwd_forms_ab.txt has the other nets; W = 16 was
+// built for the measurement, and the build also had a GELU tail three instructions per pair shorter that is not in the library):
+//                      36-64-64-64-1, fp16 pieces        36-64-64-64-1, bf16 pieces
+//     N   tiles / CU    W = 4    W = 8   W = 16           W = 4    W = 8   W = 16
+//    49 152      6       15.8     15.0     20.2            17.3     18.0     22.3
+//    98 304     12       19.8     21.6     20.8            21.8     24.2     23.6
+//   131 072     16       24.9     22.4     21.8            29.9     25.5     27.5
+//   196 608     24       33.1     29.3     35.8            38.4     35.0     45.4
+//   262 144     32       46.4     41.0     39.5            53.0     48.4     47.0
+//   524 288     64       81.8     72.2     68.3            93.4     89.8     87.7
+// 2 097 152    256      283.3    258.1    257.4           356.4    331.1    330.6
+// From 16 tiles per CU on W = 8 is the fastest or within 6 % of it for every net; at 12 and below W = 4 is.
+template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16 = false>
+int launch_fwd_split_ch(const MlpPlan& p, const SplitPlan& sp, int64_t N, const float* X, const float* packed,
+                     const unsigned char* skip, float* Y, hipStream_t st) {
+  constexpr bool WIDE = split_wide_built<T1, T2, T3, OUT_T, FINAL_DOT, SPLIT_WIDE_W>;
+  int form = g_fwd_form_forced;
+  if (form == 0) {
+    const int64_t ntiles = (N + 31) / 32;
+    form = WIDE && ntiles >= (int64_t)SPLIT_WIDE_MIN_TILES_PER_CU * mlp_device_cus() ? SPLIT_WIDE_W : 4;
+  }
+  if (form == 4)
+    return launch_fwd_split_form<4, mlp_fwd_split_kernel<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16>>(p, sp, N, X, packed, skip, Y, st);
+  if (form == 8) return launch_fwd_split_wide<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16, 8>(p, sp, N, X, packed, skip, Y, st);
+  return launch_fwd_split_wide<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16, 16>(p, sp, N, X, packed, skip, Y, st);
 }
 
 template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT>
@@ -490,5 +597,17 @@ int psdf_mlp_forward_masked(int n_layers, const int* dims, int64_t N, const floa
                             const unsigned char* skip, float* Y, void* stream) {
   return mlp_forward_impl(n_layers, dims, N, X, packed, skip, Y, stream);
 }
+
+// Test and A/B hook: forces the workgroup form of the split forward (waves per workgroup: 4, 8 or 16; 0 = the launch policy
+// decides) for the process, until it is called again.  A forward whose net has no kernel of the forced form returns -2 and
+// launches nothing.  -1 for any other value.
+int psdf_mlp_forward_set_form(int waves) {
+  if (waves != 0 && waves != 4 && waves != 8 && waves != 16) return PSDF_ERR_ARG;
+  g_fwd_form_forced = waves;
+  return PSDF_OK;
+}
+
+// Waves per workgroup of the last split forward launch (0: none yet).  psdf_last_path(2) keeps naming the arithmetic.
+int psdf_mlp_forward_last_form(void) { return g_fwd_form_last; }
 
 }  // extern "C"

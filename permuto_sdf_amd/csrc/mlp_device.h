@@ -131,7 +131,13 @@ __device__ __forceinline__ void dense_chain(const f32x16 (&in)[TI], f32x16 (&out
 // D tile of layer l = B operand of layer l+1.  Lane (sample n = lane & 31, half h = lane >> 5) supplies, for k-step s
 // of input tile ti = s >> 1, its registers r = 8 (s & 1) + j, j = 0..7, i.e. the neurons 32 ti + row_of(r, h); the
 // weight image is permuted to match.  Layer 0 reads features k = 16 s + 8 h + j of the feature-major input.
-constexpr int SPLIT_LDS_MAX = 80 * 1024;  // two workgroups per CU
+// Half of the 160 KB of LDS of a CU, so two workgroups fit.  Which forms of the forward (mlp.hip) fit how often per CU, for the
+// 68.6 KB image of 36-64-64-64-1 (at most 76.1 KB with 64 inputs and 4 outputs; registers allow four waves per SIMD):
+//   W = 4  (mlp_fwd_split_kernel, 256 threads)      twice:  8 waves per CU, TWO per SIMD -- the image, not the registers, limits it
+//   W = 8  (mlp_fwd_split_wg_kernel, 512 threads)   twice: 16 waves per CU, four per SIMD
+//   W = 16 (mlp_fwd_split_wg_kernel, 1024 threads)  once:  16 waves per CU, four per SIMD (the registers limit it)
+// The 32-wide nets (20 KB images) fit the four-wave form four times and more; their registers (up to 161) limit them.
+constexpr int SPLIT_LDS_MAX = 80 * 1024;
 
 struct SplitPlan {
   int ok;            // the image fits SPLIT_LDS_MAX (else the fp32 MFMA kernel is used)

@@ -79,6 +79,18 @@ def mlp_forward_raw(dims, x_fm, packed, skip=None, out=None, f16=False):
     return y
 
 
+def set_forward_form(waves):
+    """Force the workgroup form of the split forward kernels for this process: `waves` per workgroup (4, 8 or 16), 0 = the
+    library's launch policy decides again.  A forward of a net that has no kernel of the forced form then fails with -2
+    (unsupported) without launching.  For tests and A/B measurements (psdf_mlp_forward_set_form)."""
+    L.call("psdf_mlp_forward_set_form", L.c_i(waves))
+
+
+def last_forward_form():
+    """waves per workgroup of the last split forward launch (0: none yet)"""
+    return int(L.lib().psdf_mlp_forward_last_form())
+
+
 _wide_f16_fn = None
 
 
