@@ -638,6 +638,43 @@ int psdf_mesh_nn_cooperative(const float* queries, int64_t nq, const int32_t* qu
 int psdf_mesh_nn_ring(const float* queries, int64_t nq, const float* refs, int64_t nr, const int32_t* cell_start, const float*
     origin_edge, const int* dims, float max_dist, float* dist, int32_t* idx, const uint8_t* open, void* stream);
 
+/* ---- image_eval.hip ---- */
+/* The image scores of the reference's held-out views (permuto_sdf_py/experiments/evaluation/evaluate_psnr.py: piq.psnr and
+   piq.ssim on both images times the mask) on device tensors, accumulated in float64 without floating-point atomics: the same
+   input gives the same bits on every run.  An image is a logical (N, C, H, W) tensor read in place: `x` a device pointer to its
+   first element, `x_u8` 0: fp32 elements, 1: uint8 elements (v stands for v / 255.0), `x_strides` a HOST array of the four
+   element strides (>= 0; an NHWC buffer viewed as NCHW is read without a copy).  pred and gt may differ in element type and
+   strides.  mask: NULL, or a logical (N, 1, H, W) tensor given the same way (its channel stride is not read); it multiplies both
+   images, data_range (> 0) divides both, in double.  The entries allocate nothing and never synchronise; N = 0 returns 0 before
+   any pointer check. */
+/* host only: the launch plan of psdf_image_ssim (csrc/image_eval_plan.h) -> out [PSDF_IMAGE_EVAL_PLAN_FIELDS] int64:
+   0 the pooling factor f = max(1, round_half_even(min(H, W) / 256)) (1 when downsample = 0); 1, 2 the pooled extents H / f,
+   W / f; 3, 4 the extents of the map, pooled - kernel_size + 1; 5, 6 the map entries per workgroup tile (rows, columns); 7, 8 the
+   tiles along the map's rows and columns; 9 bytes of psdf_image_ssim's workspace; 10 partial sums per image of
+   psdf_image_sq_diff; 11 bytes of its workspace; 12 the largest kernel_size; 13 bytes of LDS of an SSIM workgroup.
+   -1: N < 0, an extent < 1, kernel_size even, < 1 or above out[12], or a pooled side shorter than kernel_size; -2: more than
+   2^31 - 1 workgroups */
+#define PSDF_IMAGE_EVAL_PLAN_FIELDS 14
+int psdf_image_eval_plan(int64_t N, int C, int H, int W, int kernel_size, int downsample, int64_t* out);
+/* host only: partial sums per image of psdf_image_sq_diff, ceil(H W / 2048) (-1: an extent < 1) -- the one plan value an image
+   smaller than the SSIM window still has */
+int64_t psdf_image_sq_diff_partials(int H, int W);
+/* replaces: the sum inside piq.psnr's mean squared error.  out [N] float64 <- sum over (c, h, w) of (pred - gt)^2 of the masked,
+   range-divided values; workspace [N * psdf_image_sq_diff_partials(H, W)] float64: one partial per workgroup, written in a fixed
+   order and added in a fixed order by a finishing launch */
+int psdf_image_sq_diff(const void* pred, int pred_u8, const int64_t* pred_strides, const void* gt, int gt_u8, const int64_t*
+    gt_strides, const void* mask, int mask_u8, const int64_t* mask_strides, int64_t N, int C, int H, int W, double data_range,
+    double* workspace, double* out, void* stream);
+/* replaces: piq.ssim (average pooling by f with floor mode, the kernel_size x kernel_size Gaussian window of kernel_sigma over
+   valid positions only, c1 = k1^2, c2 = k2^2, mean over the map and then over channels).  One fused pass per (image, channel,
+   tile): pooled values, the horizontally filtered moments and the reduction live in LDS only.  out [N] float64 <- the score of
+   every image; map: NULL, or [N, C, out[3], out[4]] float64 <- the map itself; workspace: out[9] bytes.  -1 also for a
+   non-positive kernel_sigma or data_range and a NULL image, workspace or out */
+int psdf_image_ssim(const void* pred, int pred_u8, const int64_t* pred_strides, const void* gt, int gt_u8, const int64_t*
+    gt_strides, const void* mask, int mask_u8, const int64_t* mask_strides, int64_t N, int C, int H, int W, double data_range,
+    int kernel_size, double kernel_sigma, double k1, double k2, int downsample, double* workspace, double* out, double* map,
+    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ Host side: Python/PyTorch-ROCm (device memory, streams, autograd, torch.distribu
 HIP kernels through the C-ABI library declared in include/psdf.h.  No CPU fallback exists.
 """
 from . import _lib
+from . import image_eval
 from .encoding import PermutoEncoding, Coarse2Fine
 from .mlp import FusedMLP, LipshitzMLP
 
-__all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP"]
+__all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval"]
