@@ -675,6 +675,46 @@ int psdf_image_ssim(const void* pred, int pred_u8, const int64_t* pred_strides, 
     int kernel_size, double kernel_sigma, double k1, double k2, int downsample, double* workspace, double* out, double* map,
     void* stream);
 
+/* ---- frame_rays.hip, frame_composite.hip ---- */
+/* A held-out view rendered volumetrically, a chunk of pixels at a time, into planar [3, H, W] / [1, H, W] fp32 images on the
+   device.  Pixel p of an H x W frame is (x, y) = (p % W, p / W) with its centre at +0.5; a chunk is the pixel range
+   [pixel_first, pixel_first + nr_rays) and ray r of a chunk's sample container belongs to pixel pixel_first + r.  The entries
+   allocate nothing and never synchronise; nr_rays <= 0 returns 0 before any pointer check; -1 for a NULL pointer, an extent < 1
+   or a range outside the frame, -2 for H W >= 2^31. */
+/* host only: the chunking of a frame (csrc/frame_plan.h) -> out [PSDF_FRAME_PLAN_FIELDS] int64: 0 rays per chunk, the largest
+   multiple of 64 with rays * max_nr_samples_per_ray <= pool_samples (the condition under which no ray of a chunk overflows the
+   march's sample pool), at most H W; 1 the number of chunks; 2 the rays of the last chunk.
+   replaces: the fixed chunk_size = 3000 of permuto_sdf_py/experiments/evaluation/create_my_images.py:80 and the chunk
+   arithmetic of run_net_in_chunks (permuto_sdf_py/train_permuto_sdf.py:174-176).
+   -1: H, W or max_nr_samples_per_ray < 1, pool_samples < 64 * max_nr_samples_per_ray, out NULL; -2: H W >= 2^31 */
+#define PSDF_FRAME_PLAN_FIELDS 3
+int psdf_frame_plan(int H, int W, int max_nr_samples_per_ray, int64_t pool_samples, int64_t* out);
+/* replaces: create_rays_from_frame (permuto_sdf_py/utils/nerf_utils.py:459-500) for a range of pixels.  K: device pointer to
+   the 9 floats of one row-major intrinsic matrix, tf_world_cam: to the 16 floats of one row-major [R|t] (what a reel holds per
+   image); origins [nr_rays, 3], dirs [nr_rays, 3].  The arithmetic is psdf_random_rays_from_reel's: the ray of a pixel has the
+   same bits from both. */
+int psdf_frame_rays(int H, int W, const float* K, const float* tf_world_cam, int64_t pixel_first, int nr_rays, float* origins,
+    float* dirs, void* stream);
+/* replaces: per chunk, compute_weights + integrate of the colours and of the SDF gradients + F.normalize of run_net
+   (permuto_sdf_py/train_permuto_sdf.py:137-142), the list appends, torch.cat and lin2nchw of run_net_in_chunks (:190-207), and
+   rotate_normals_to_cam_frame (permuto_sdf_py/utils/common_utils.py:573-589).  Ray-index and sample arguments as
+   psdf_neus_composite_forward; rot_cam_world: device pointer to the 9 floats of the row-major rotation of tf_cam_world, read
+   when normals_cam_img is given.  Written at pixel pixel_first + ray: rgb_img [3, H, W] <- sum w rgb; normals_img [3, H, W] <-
+   G / max(|G|, 1e-12), G = sum w gradient; normals_cam_img [3, H, W] or NULL <- normalize(R n); weights_sum_img [1, H, W] <-
+   sum w; transmittance [nr_rays] <- the background transmittance of every ray of the chunk.  Empty and overflowed rays: 0, 0,
+   0, 0 and 1 (:124-129).  Any ray length.  With max_nr_samples = 0 the sample pointers may be NULL. */
+int psdf_frame_composite_neus(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, const float* sdf,
+    const float* dirs, const float* gradients, const float* dt, const float* rgb, const float* inv_s, float cos_anneal_ratio,
+    const float* rot_cam_world, int H, int W, int64_t pixel_first, float* rgb_img, float* normals_img, float* normals_cam_img,
+    float* weights_sum_img, float* transmittance, void* stream);
+/* replaces: the background half of run_net (permuto_sdf_py/train_permuto_sdf.py:156-162) and its share of the cat / lin2nchw
+   of run_net_in_chunks.  Arguments as psdf_nerf_composite_forward; transmittance [nr_rays] and the foreground already in
+   rgb_img come from psdf_frame_composite_neus of the same chunk.  rgb_bg_img [3, H, W] <- t * (sum w rgb); rgb_img <- rgb_img +
+   that.  Rays without background samples add 0. */
+int psdf_frame_composite_nerf(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, const float*
+    raw_density, const float* dt, const float* rgb, const float* transmittance, int H, int W, int64_t pixel_first, float*
+    rgb_img, float* rgb_bg_img, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ using namespace psdf;
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------- forward
+// (frame_composite.hip restates this loop, and the loop of nerf_composite_fwd_kernel below, with image planes as outputs: a change
+//  of the arithmetic here belongs there too -- tests/test_gpu_frame.py compares the two bit for bit)
 __global__ void __launch_bounds__(PSDF_BLOCK)
     neus_composite_fwd_kernel(int nr_rays, RayIndex ri, const float* __restrict__ sdf, const float* __restrict__ dirs,
                               const float* __restrict__ gradients, const float* __restrict__ dt, const float* __restrict__ rgb,

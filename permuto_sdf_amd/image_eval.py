@@ -13,7 +13,8 @@ in float64 over tensors that are already on the device, however they were render
 Images are (N, C, H, W) or (C, H, W) tensors, float32 or uint8 (a uint8 value v stands for v / 255), each read in place through
 its own strides: an NHWC buffer passed as `buf.permute(0, 3, 1, 2)` costs no copy, and `pred` and `gt` may differ in dtype and
 layout.  The mask is (N, 1, H, W) or (1, 1, H, W): float32, bool, or uint8 read like an 8-bit image (255 keeps a pixel).  Results are float64 tensors on the
-device; nothing here reads them back.  Rendering the views and reading or writing image files stay the caller's business.
+device; nothing here reads them back.  The views come from `render.FrameRenderer.render_views` or from anywhere else; reading or
+writing image files stays the caller's business.
 """
 import ctypes
 
