@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 
 EQUAL_COUNTS = (1, 2, 48, 64, 65, 128, 129, 192, 193, 256)
+BORDER_COUNTS = (0, 1, 2, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 321, 0, 40)
 
 
 def container(name, seed=0):
@@ -12,7 +13,10 @@ def container(name, seed=0):
     equalK      : R rays of K samples
     ragged      : 1..256 samples, 30 empty rays
     overflow    : ragged, the pool ends inside the fourth ray from the end (that ray and the three behind it pass max_nr_samples)
-    capK        : ragged, at most K samples (K = 64 / 128 / 256), some empty rays"""
+    capK        : ragged, at most K samples (K = 64 / 128 / 256), some empty rays
+    bordersK    : every 64-sample chunk border -1 / +0 / +1 up to K samples and two empty rays, then rays of 70 and 40 samples that
+                  pass max_nr_samples (the pool ends 17 samples into the first of them): the smallest container that reaches every
+                  chunk count of the ray kernels (tests/test_gpu_composite_parent_bits.py)"""
     g = torch.Generator().manual_seed(1000 + seed)
     equal, fixed = False, 0
     if name.startswith("equal"):
@@ -32,6 +36,9 @@ def container(name, seed=0):
         counts = torch.randint(1, cap + 1, (R,), generator=g)
         counts[:4] = torch.tensor([cap, 1, min(48, cap), max(1, cap - 63)])
         counts[4 + torch.randperm(R - 4, generator=g)[:10]] = 0
+    elif name.startswith("borders"):
+        cap = int(name[7:])
+        counts = torch.tensor([n for n in BORDER_COUNTS if n <= cap] + [70, 40])
     else:
         raise ValueError(name)
     ends = torch.cumsum(counts, 0)
@@ -39,8 +46,12 @@ def container(name, seed=0):
     N = int(ends[-1])
     if name == "overflow":
         N = int(starts[-4]) + 17
+    elif name.startswith("borders"):
+        N = int(starts[-2]) + 17
+    # (the longest ray that is rendered: the two overflowed rays of a borders container are skipped)
+    max_per_ray = int(counts[:-2].max()) if name.startswith("borders") else int(counts.max())
     return dict(name=name, counts=counts, start_end=torch.stack([starts, ends], 1).to(torch.int32), N=N, total=int(ends[-1]),
-                equal=equal, fixed=fixed, max_per_ray=int(counts.max()), R=len(counts))
+                equal=equal, fixed=fixed, max_per_ray=max_per_ray, R=len(counts))
 
 
 def per_sample_ray(c):

@@ -3,15 +3,15 @@
 // background) and run_net_in_chunks does with the results (:190-207: list appends, torch.cat, lin2nchw), and
 // rotate_normals_to_cam_frame (permuto_sdf_py/utils/common_utils.py:573-589) for the camera-frame normals.
 //
-// A wave owns a ray and sweeps its contiguous samples in chunks of 64, with the structure and the arithmetic of
-// neus_composite_fwd_kernel / nerf_composite_fwd_kernel (composite_fused.hip): the same section-point opacity, the same product
-// scan with a carry, per-lane partial sums and one wave sum per quantity at the end.  From the ONE sweep over the samples the
-// foreground kernel forms
+// A wave owns a ray and sweeps its contiguous samples in chunks of 64 through sweep() of composite_device.h, the sweep of
+// neus_composite_fwd_kernel / nerf_composite_fwd_kernel (composite_fused.hip): section-point or NeRF opacity, product scan with
+// a carry; per-lane partial sums and one wave sum per quantity at the end.  From the ONE sweep over the samples the foreground
+// kernel forms
 //   radiance           sum w rgb                                   (integrate_fwd_kernel's order)
 //   weight sum         sum w                                       (sum_ray_fwd_kernel's order)
 //   gradient integral  G = sum w gradient                          (integrate_fwd_kernel's order; the gradients are read for the
 //                                                                   opacity anyway: no extra bytes)
-//   world normal       G / max(|G|, 1e-12)                         (normalize3's forward, neus.hip)
+//   world normal       G / max(|G|, 1e-12)                         (normalize_eps, as normalize3's forward)
 //   camera normal      normalize(R n), R the rotation of tf_cam_world (optional)
 //   bg transmittance   the scan's carry, to a per-chunk [R] buffer that the background kernel reads
 // and lane 0 stores them at pixel pixel_first + ray of the [3, H, W] / [1, H, W] planes.  Empty and overflowed rays hold
@@ -27,13 +27,6 @@
 using namespace psdf;
 
 namespace {
-
-// F.normalize(x, dim=-1): the expressions of normalize_eps (neus.hip)
-__device__ __forceinline__ v3 normalized(v3 x) {
-  const float norm = sqrtf(dot3(x, x));
-  const float denom = fmaxf(norm, 1e-12f);
-  return v3{x.x / denom, x.y / denom, x.z / denom};
-}
 
 __device__ __forceinline__ void st_planes(float* __restrict__ img, int64_t plane, int64_t pixel, v3 a) {
   img[pixel] = a.x;
@@ -65,33 +58,24 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       }
       continue;
     }
-    const int n = e - s;
-    float carry = 1.f, r = 0.f, g = 0.f, b = 0.f, ws = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
-    for (int base = 0; base < n; base += 64) {
-      const int i = base + lane;
-      const bool in = i < n;
-      const int64_t m = s + (in ? i : n - 1);
-      const v3 grad = ld3(gradients + 3 * m);
-      const Section sc = section(sdf[m], ld3(dirs + 3 * m), grad, dt[m], inv_s, cos_anneal_ratio);
-      const float a = clip01(sc.q);
-      const float om = (1.0f - a) + 1e-7f;
-      const float fac = (i < n - 1) ? om : 1.f;
-      const float incl = wave_incl_scan_mul(fac);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.f;
-      const float T = carry * excl;
-      carry = carry * __shfl(incl, 63, 64);
-      if (in) {
-        const float w = a * T;
-        r += w * rgb[3 * m];
-        g += w * rgb[3 * m + 1];
-        b += w * rgb[3 * m + 2];
-        ws += w;
-        gx += w * grad.x;
-        gy += w * grad.y;
-        gz += w * grad.z;
-      }
-    }
+    float r = 0.f, g = 0.f, b = 0.f, ws = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+    v3 grad;                                // of the sample in flight: read ONCE, for the opacity and for the integral
+    const float T_bg = sweep(
+        s, e - s, lane,
+        [&](int64_t m) {
+          grad = ld3(gradients + 3 * m);
+          return clip01(section(sdf[m], ld3(dirs + 3 * m), grad, dt[m], inv_s, cos_anneal_ratio).q);
+        },
+        [&](int64_t m, float a, float T) {
+          const float w = a * T;
+          r += w * rgb[3 * m];
+          g += w * rgb[3 * m + 1];
+          b += w * rgb[3 * m + 2];
+          ws += w;
+          gx += w * grad.x;
+          gy += w * grad.y;
+          gz += w * grad.z;
+        });
     r = wave_sum(r);
     g = wave_sum(g);
     b = wave_sum(b);
@@ -101,20 +85,18 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     gz = wave_sum(gz);
     if (lane == 0) {
       st_planes(rgb_img, plane, pixel, mk3(r, g, b));
-      const v3 nrm = normalized(mk3(gx, gy, gz));
+      const v3 nrm = normalize_eps(mk3(gx, gy, gz)).y;
       st_planes(normals_img, plane, pixel, nrm);
       if (normals_cam_img) {
         const v3 c = mk3(rot[0] * nrm.x + rot[1] * nrm.y + rot[2] * nrm.z, rot[3] * nrm.x + rot[4] * nrm.y + rot[5] * nrm.z,
                          rot[6] * nrm.x + rot[7] * nrm.y + rot[8] * nrm.z);
-        st_planes(normals_cam_img, plane, pixel, normalized(c));
+        st_planes(normals_cam_img, plane, pixel, normalize_eps(c).y);
       }
       weights_sum_img[pixel] = ws;
-      transmittance[ray] = carry;
+      transmittance[ray] = T_bg;
     }
   }
 }
-
-__device__ __forceinline__ float softplus20(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 
 __global__ void __launch_bounds__(PSDF_BLOCK)
     frame_composite_nerf_kernel(int nr_rays, RayIndex ri, const float* __restrict__ raw, const float* __restrict__ dt,
@@ -126,27 +108,14 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     ri.get(ray, s, e);
     float r = 0.f, g = 0.f, b = 0.f;
     if (ri.valid(s, e)) {
-      const int n = e - s;
-      float carry = 1.f;
-      for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool in = i < n;
-        const int64_t m = s + (in ? i : n - 1);
-        const float a = 1.0f - expf(-softplus20(raw[m]) * dt[m]);
-        const float om = (1.0f - a) + 1e-7f;
-        const float fac = (i < n - 1) ? om : 1.f;
-        const float incl = wave_incl_scan_mul(fac);
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.f;
-        const float T = carry * excl;
-        carry = carry * __shfl(incl, 63, 64);
-        if (in) {
-          const float w = a * T;
-          r += w * rgb[3 * m];
-          g += w * rgb[3 * m + 1];
-          b += w * rgb[3 * m + 2];
-        }
-      }
+      sweep(
+          s, e - s, lane, [&](int64_t m) { return nerf_alpha(raw[m], dt[m]).a; },
+          [&](int64_t m, float a, float T) {
+            const float w = a * T;
+            r += w * rgb[3 * m];
+            g += w * rgb[3 * m + 1];
+            b += w * rgb[3 * m + 2];
+          });
       r = wave_sum(r);
       g = wave_sum(g);
       b = wave_sum(b);

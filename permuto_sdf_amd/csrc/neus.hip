@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     const Section s = section(sdf[n], ld3(dirs + 3 * n), ld3(gradients + 3 * n), dt[n], inv_s, cos_anneal_ratio);
     const float a = clip01(s.q);
     alpha[n] = a;
-    if (one_minus_alpha) one_minus_alpha[n] = (1.0f - a) + 1e-7f;         // what cumprod_alpha2transmittance is fed
+    if (one_minus_alpha) one_minus_alpha[n] = one_minus(a);               // what cumprod_alpha2transmittance is fed
   }
 }
 
@@ -41,23 +41,10 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     const v3 dir = ld3(dirs + 3 * n);
     const float d = dt[n];
     const Section s = section(sdf[n], dir, ld3(gradients + 3 * n), d, inv_s, r);
-    // clip(q, 0, 1) passes the gradient inside the closed interval (torch.clamp).  q lies in (0, 1] for finite inputs with
-    // dt >= 0 (clip01 in composite_device.h): the 0 arm is reached by a NaN q alone, and g_sdf is NaN there either way
-    const float gq = (s.q >= 0.0f && s.q <= 1.0f) ? g_alpha[n] : 0.0f;
-    const float den = s.c + 1e-5f;
-    const float g_p = gq / den;
-    const float g_c = -gq * (s.p + 1e-5f) / (den * den);
-    const float g_up = (g_p + g_c) * (s.pc * (1.0f - s.pc));              // through sigmoid(ep * inv_s)
-    const float g_un = -g_p * (s.nc * (1.0f - s.nc));                     // through sigmoid(en * inv_s)
-    const float g_ep = g_up * inv_s, g_en = g_un * inv_s;
-    gs_acc += g_up * s.ep + g_un * s.en;
-    g_sdf[n] = g_ep + g_en;
-    if (g_gradients) {
-      const float g_ic = (g_en - g_ep) * (d * 0.5f);
-      // ic = -(relu(pre_a) (1-r) + relu(pre_b) r);  pre_a = -tc/2 + 1/2;  pre_b = -tc
-      const float g_tc = g_ic * ((s.pre_a > 0.f ? 0.5f * (1.0f - r) : 0.f) + (s.pre_b > 0.f ? r : 0.f));
-      st3(g_gradients + 3 * n, g_tc * dir);
-    }
+    const SectionGrad g = section_backward(s, g_alpha[n], d, inv_s, r);
+    gs_acc += g.g_inv_s;
+    g_sdf[n] = g.g_sdf;
+    if (g_gradients) st3(g_gradients + 3 * n, g.g_tc * dir);
   }
   if (g_inv_s) {
     gs_acc = wave_sum(gs_acc);
@@ -114,33 +101,13 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
 // ---------------------------------------------------------------------------------------------------------------------
 // More elementwise chains of the training step, one launch per direction each (the torch forms are 5-25 launches forward
 // and about twice that backward; the step is host bound, csrc/../train_step.py):
-//   normalize3      F.normalize(x, dim=-1) (eps 1e-12)                                       models.py:272,367 ...
+//   normalize3      F.normalize(x, dim=-1) (normalize_eps, composite_device.h)                models.py:272,367 ...
 //   curvature shift points + eps * cross(normalize(g), normalize(rand))                      models.py:266-277
 //   curvature loss  scale * sum acos(clamp(n(g) . n(g2), -1+1e-6, 1-1e-6)) / pi              models.py:282-289, train_permuto_sdf.py:363
 //   offsurface loss scale * sum exp(-100 |sdf|)                                              train_permuto_sdf.py:372-375
 //   nerf alpha      alpha = 1 - exp(-softplus(raw) dt), one_minus = 1 - alpha + 1e-7        models.py:520, volume_rendering_modules.py:72-86
+//                   (nerf_alpha / nerf_alpha_backward, composite_device.h)
 // All fp32, expressions in the order torch evaluates them.
-struct Nrm {
-  v3 y;
-  float norm, denom;
-};
-__device__ __forceinline__ Nrm normalize_eps(v3 x) {
-  Nrm r;
-  r.norm = sqrtf(dot3(x, x));
-  r.denom = fmaxf(r.norm, 1e-12f);
-  r.y = v3{x.x / r.denom, x.y / r.denom, x.z / r.denom};
-  return r;
-}
-// gradient of y = x / max(|x|, eps) for an upstream gy
-__device__ __forceinline__ v3 normalize_bwd(const Nrm& n, v3 gy) {
-  const float inv = 1.0f / n.denom;
-  v3 g = inv * gy;
-  if (n.norm > 1e-12f) {   // the clamp passes the gradient of the norm only above eps
-    const float s = dot3(gy, n.y) * inv;
-    g = g - s * n.y;
-  }
-  return g;
-}
 __device__ __forceinline__ v3 cross3(v3 a, v3 b) {
   return v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
@@ -224,24 +191,20 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   block_sum_atomic(acc, scale, loss);
 }
 
-__device__ __forceinline__ float softplus20(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 // forward (g_alpha == NULL): alpha, one_minus;  backward: g_raw = d / d raw of (alpha . g_alpha + one_minus . g_one_minus)
 __global__ void __launch_bounds__(PSDF_BLOCK)
     nerf_alpha_kernel(int64_t N, const float* __restrict__ raw, const float* __restrict__ dt, float* __restrict__ alpha,
-                      float* __restrict__ one_minus, const float* __restrict__ g_alpha,
+                      float* __restrict__ one_minus_alpha, const float* __restrict__ g_alpha,
                       const float* __restrict__ g_one_minus, float* __restrict__ g_raw) {
   for (int64_t n = (int64_t)blockIdx.x * PSDF_BLOCK + threadIdx.x; n < N; n += (int64_t)gridDim.x * PSDF_BLOCK) {
     const float x = raw[n], d = dt[n];
-    const float dens = softplus20(x);
-    const float e = expf(-dens * d);
+    const NerfAlpha o = nerf_alpha(x, d);
     if (!g_raw) {
-      const float a = 1.0f - e;
-      alpha[n] = a;
-      one_minus[n] = (1.0f - a) + 1e-7f;
+      alpha[n] = o.a;
+      one_minus_alpha[n] = one_minus(o.a);
     } else {
       const float ga = (g_alpha ? g_alpha[n] : 0.f) - (g_one_minus ? g_one_minus[n] : 0.f);   // one_minus = 1 - alpha + 1e-7
-      const float g_dens = ga * e * d;                                                         // alpha = 1 - exp(-dens dt)
-      g_raw[n] = g_dens * (x > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-x)));                       // softplus' = sigmoid
+      g_raw[n] = nerf_alpha_backward(ga, o.e, x, d);
     }
   }
 }

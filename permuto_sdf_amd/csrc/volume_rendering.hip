@@ -27,18 +27,14 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     ri.get(ray, s, e);
     if (!ri.valid(s, e)) continue;
     const int n = e - s;
-    float carry = 1.f;
+    Transmittance tr;
     for (int base = 0; base < n; base += 64) {
       const int i = base + lane;
       // the last sample's factor never enters the product (bg transmittance == T of the last sample)
-      const float a = (i < n - 1) ? alpha[s + i] : 1.f;
-      const float incl = wave_incl_scan_mul(a);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.f;
-      if (i < n) trans[s + i] = carry * excl;
-      carry = carry * __shfl(incl, 63, 64);
+      const float T = tr.step((i < n - 1) ? alpha[s + i] : 1.f, lane);
+      if (i < n) trans[s + i] = T;
     }
-    if (lane == 0) bg[ray] = carry;
+    if (lane == 0) bg[ray] = tr.carry;
   }
 }
 
@@ -179,7 +175,6 @@ __device__ __forceinline__ float map_range(float v, float in0, float in1, float 
   const float c = fmaxf(in0, fminf(in1, v));
   return out0 + ((out1 - out0) / (in1 - in0)) * (c - in0);
 }
-__device__ __forceinline__ float sigmoidf(float x) { return (float)(1.0 / (1.0 + (double)expf(-x))); }
 
 __global__ void __launch_bounds__(PSDF_BLOCK)
     sdf2alpha_kernel(int nr_rays, RayIndex ri, const float* __restrict__ ray_fixed_dt, const float* __restrict__ dt,
@@ -194,17 +189,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     if (dynamic_inv_s) inv_s = map_range(ray_fixed_dt[ray], 0.0001f, 0.01f, 1024.f, 64.f);
     inv_s = inv_s * inv_s_mult;
     const int n = e - s;
-    for (int i = lane; i < n - 1; i += 64) {
-      const float d = dt[s + i];
-      const float prev = sdf[s + i], next = sdf[s + i + 1];
-      const float mid = (float)((double)(prev + next) * 0.5);
-      float cosv = (next - prev) / fmaxf(d, 1e-6f);
-      cosv = clampf(cosv, -1e3f, 0.0f);
-      const float half = (float)((double)(cosv * d) * 0.5);
-      const float prev_cdf = sigmoidf((mid - half) * inv_s);
-      const float next_cdf = sigmoidf((mid + half) * inv_s);
-      alpha[s + i] = (float)(((double)(prev_cdf - next_cdf) + 1e-6) / ((double)prev_cdf + 1e-6));
-    }
+    for (int i = lane; i < n - 1; i += 64) alpha[s + i] = sdf2alpha_midpoint(sdf[s + i], sdf[s + i + 1], dt[s + i], inv_s);
   }
 }
 
@@ -228,35 +213,17 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     if (dynamic_inv_s) inv_s = map_range(ray_fixed_dt[ray], 0.0001f, 0.01f, 1024.f, 64.f);
     inv_s = inv_s * inv_s_mult;
     const int n = e - s;
-    float carry = 1.f, acc = 0.f;
-    for (int base = 0; base < n; base += 64) {
-      const int i = base + lane;
-      float a = 0.f;                                   // the last sample of a ray keeps alpha 0 (sdf2alpha)
-      if (i < n - 1) {
-        const float d = dt[s + i];
-        const float prev = sdf[s + i], next = sdf[s + i + 1];
-        const float mid = (float)((double)(prev + next) * 0.5);
-        float cosv = (next - prev) / fmaxf(d, 1e-6f);
-        cosv = clampf(cosv, -1e3f, 0.0f);
-        const float half = (float)((double)(cosv * d) * 0.5);
-        const float prev_cdf = sigmoidf((mid - half) * inv_s);
-        const float next_cdf = sigmoidf((mid + half) * inv_s);
-        a = (float)(((double)(prev_cdf - next_cdf) + 1e-6) / ((double)prev_cdf + 1e-6));
-        a = a < 0.f ? 0.f : (a > 1.f ? 1.f : a);       // torch.clip(0, 1): a NaN stays a NaN
-      }
-      const float om = (1.f - a) + 1e-7f;              // 1 - alpha + 1e-7
-      const float f = (i < n - 1) ? om : 1.f;          // cumprod_fwd_kernel: the last sample's factor never enters
-      const float incl = wave_incl_scan_mul(f);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.f;
-      const float T = carry * excl;
-      carry = carry * __shfl(incl, 63, 64);
-      if (i < n) {
-        const float w = a * T;
-        cdf[s + i] = w;
-        acc += w;                                      // sum_ray_fwd_kernel: per-lane partials over the chunks, then the wave sum
-      }
-    }
+    float acc = 0.f;
+    sweep(
+        s, n, lane,
+        [&](int64_t m) {                               // the last sample of a ray keeps alpha 0 (sdf2alpha)
+          return m < e - 1 ? clip01(sdf2alpha_midpoint(sdf[m], sdf[m + 1], dt[m], inv_s)) : 0.f;
+        },
+        [&](int64_t m, float a, float T) {
+          const float w = a * T;
+          cdf[m] = w;
+          acc += w;                                    // sum_ray_fwd_kernel: per-lane partials over the chunks, then the wave sum
+        });
     const float total = wave_sum(acc);
     const float den = total < 1e-6f ? 1e-6f : total;   // torch.clamp(min = 1e-6) (NaN stays NaN)
     float csum = 0.f;
@@ -305,17 +272,14 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       continue;
     }
     const int n = e - s;
-    float T = 1.f, r = 0.f, g = 0.f, b = 0.f, dep = 0.f;
+    Transmittance tr;
+    float r = 0.f, g = 0.f, b = 0.f, dep = 0.f;
     bool done = false;
     for (int base = 0; base < n && !done; base += 64) {
       const int i = base + lane;
       const bool act = i < n;
       const float a = act ? (1.f - __expf(-sigma[s + i] * dt[s + i])) : 0.f;
-      const float om = 1.f - a;
-      const float incl = wave_incl_scan_mul(om);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.f;
-      const float Ti = T * excl;  // transmittance reaching sample i
+      const float Ti = tr.step(1.f - a, lane);  // transmittance reaching sample i
       const unsigned long long dead = __ballot(act && Ti < 1e-4f);
       const int first_dead = dead ? (int)__ffsll((long long)dead) - 1 : 64;
       const bool use = act && lane < first_dead;
@@ -328,11 +292,9 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
         dep += wi * z[s + i];
       }
       if (dead) {
-        // T after the last processed sample = T reaching the first dead one
-        T = __shfl(Ti, first_dead, 64);
+        // the product freezes: T after the last processed sample = T reaching the first dead one
+        tr.carry = __shfl(Ti, first_dead, 64);
         done = true;
-      } else {
-        T = T * __shfl(incl, 63, 64);
       }
     }
     r = wave_sum(r);
@@ -344,7 +306,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       pred_rgb[3 * ray + 1] = g;
       pred_rgb[3 * ray + 2] = b;
       pred_depth[ray] = dep;
-      bg[ray] = T;
+      bg[ray] = tr.carry;
     }
   }
 }
@@ -364,7 +326,8 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
     const float gx = grad_pred[3 * ray], gy = grad_pred[3 * ray + 1], gz = grad_pred[3 * ray + 2];
     const float fx = pred_rgb[3 * ray], fy = pred_rgb[3 * ray + 1], fz = pred_rgb[3 * ray + 2];
     const float gbg = grad_bg[ray], lastT = bg[ray];
-    float T = 1.f, ux = 0.f, uy = 0.f, uz = 0.f;  // colour integrated up to (and including) the previous chunk
+    Transmittance tr;
+    float ux = 0.f, uy = 0.f, uz = 0.f;  // colour integrated up to (and including) the previous chunk
     bool done = false;
     for (int base = 0; base < n && !done; base += 64) {
       const int i = base + lane;
@@ -372,10 +335,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       const float d = act ? dt[s + i] : 0.f;
       const float a = act ? (1.f - __expf(-sigma[s + i] * d)) : 0.f;
       const float om = 1.f - a;
-      const float incl = wave_incl_scan_mul(om);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.f;
-      const float Ti = T * excl;
+      const float Ti = tr.step(om, lane);
       const unsigned long long dead = __ballot(act && Ti < 1e-4f);
       const int first_dead = dead ? (int)__ffsll((long long)dead) - 1 : 64;
       const bool use = act && lane < first_dead;
@@ -403,10 +363,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       ux = __shfl(px, 63, 64);
       uy = __shfl(py, 63, 64);
       uz = __shfl(pz, 63, 64);
-      if (dead)
-        done = true;
-      else
-        T = T * __shfl(incl, 63, 64);
+      if (dead) done = true;     // (the product freezes at the first dead sample)
     }
   }
 }
