@@ -318,7 +318,7 @@ __global__ void __launch_bounds__(64)
   for (int j = lane; j < in; j += 64) Wn[r * in + j] = W[r * in + j] * scale;
 }
 
-// G = dL/dWn -> dW (written) and dc[0] (ACCUMULATED).  Active rows (scale < 1): Wn = W sp / A with A = sum |W|:
+// G = dL/dWn -> dW (written) and dc[0] (ACCUMULATED).  Active rows (sp / A <= 1, the tie included): Wn = W sp / A with A = sum |W|:
 //   dW_j = G_j sp / A - (sum_k G_k W_k) sp / A^2 sign(W_j);  dsp += (sum_k G_k W_k) / A;  dc = dsp sigmoid(c)
 __global__ void __launch_bounds__(64)
     lipshitz_norm_bwd_kernel(int in, const float* __restrict__ W, const float* __restrict__ c, const float* __restrict__ G,
@@ -334,7 +334,7 @@ __global__ void __launch_bounds__(64)
   gw = psdf::wave_sum(gw);
   const float sp = softplus_t(c[0]);
   const float ratio = sp / a;
-  const bool active = ratio < 1.0f;     // torch.clamp(max=1): the gradient passes where the input is below the bound
+  const bool active = ratio <= 1.0f;    // torch.clamp(max=1): the gradient passes where the input is AT or below the bound
   for (int j = lane; j < in; j += 64) {
     const float w = W[r * in + j], g = G[r * in + j];
     const float sgn = w > 0.f ? 1.f : (w < 0.f ? -1.f : 0.f);
@@ -383,7 +383,7 @@ __global__ void __launch_bounds__(64) lipshitz_norm_multi_kernel(LipLayers p, in
   const float x = p.c[l][0];
   const float sp = softplus_t(x);
   const float ratio = sp / a;
-  const bool active = ratio < 1.0f;
+  const bool active = ratio <= 1.0f;    // as lipshitz_norm_bwd_kernel: a row at exactly 1 is differentiated
   for (int j = lane; j < in; j += 64) {
     const float w = W[r * in + j], g = G[r * in + j];
     const float sgn = w > 0.f ? 1.f : (w < 0.f ? -1.f : 0.f);

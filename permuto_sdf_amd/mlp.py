@@ -587,8 +587,10 @@ class LipshitzMLP(torch.nn.Module):
     """Lipschitz-regularised MLP of the colour network (reference: permuto_sdf_py/models/models.py:54-129, used at
     :349-350 as 111 -> 128 -> 128 -> 64 -> 3): every layer's weight is rescaled per row by
     min(1, softplus(c_i) / sum(abs(W_row))) before the Linear; GELU between layers.  Same constructor, methods and
-    parameter names as the reference class (`layers.i.weight|bias`, `lipshitz_bound_per_layer.i`).  The normalisation
-    is a handful of torch ops on <= 16 K-element tensors; the Linear/GELU stack runs in the fused MFMA evaluator."""
+    parameter names as the reference class (`layers.i.weight|bias`, `lipshitz_bound_per_layer.i`).  On the device the
+    normalisation of ALL layers is one launch per direction (`_LipshitzNormAllFunc`: lipshitz_norm_multi_kernel, csrc/mlp_wide.hip;
+    a row at exactly ratio 1 is differentiated, as torch's clamp does it); the Linear/GELU stack runs in the fused MFMA
+    evaluator.  The torch expression below (`normalization`) serves parameter bookkeeping on the CPU only."""
 
     def __init__(self, in_channels, nr_out_channels_per_layer, last_layer_linear):
         super().__init__()
