@@ -162,18 +162,24 @@ class GradBuffer:
         self.flat.zero_()
 
 
-def mlp_backward_raw(dims, x_fm, weights, biases, gy_fm, need_dx=True, need_dw=True, into=None):
+def mlp_backward_raw(dims, x_fm, weights, biases, gy_fm, need_dx=True, need_dw=True, into=None, dx=None):
     """weights/biases: the torch-layout parameters (the backward kernel builds its own LDS image from them)
     -> (dx_fm [dims[0], N] or None, [dW_l], [db_l]); need_dw=False: data gradient only (lighter kernel, empty lists);
     into = (dWs, dbs): accumulate into these instead of fresh zero-filled tensors; gy_fm = None (with need_dw=False): the unit
-    gradient of output 0, d y_0 / d x"""
+    gradient of output 0, d y_0 / d x; dx (with need_dx): a contiguous [dims[0], N] fp32 buffer that receives the data gradient
+    instead of a fresh tensor"""
     assert gy_fm is not None or not need_dw
     N = x_fm.shape[1]
     n_layers = len(dims) - 1
     dev = x_fm.device
     ws = [w.detach().contiguous() for w in weights]
     bs = [b.detach().contiguous() for b in biases]
-    dx = torch.empty((dims[0], N), dtype=torch.float32, device=dev) if need_dx else None
+    if not need_dx:
+        dx = None
+    elif dx is None:
+        dx = torch.empty((dims[0], N), dtype=torch.float32, device=dev)
+    else:
+        assert dx.shape == (dims[0], N) and dx.dtype == torch.float32 and dx.is_contiguous() and dx.device == dev
     Wp = (ctypes.c_void_p * n_layers)(*[w.data_ptr() for w in ws])
     Bp = (ctypes.c_void_p * n_layers)(*[b.data_ptr() for b in bs])
     if need_dw:

@@ -18,6 +18,8 @@ import textwrap
 import pytest
 import torch
 
+from tests.mlp_float64 import _f64_pass, _per_entry
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -67,43 +69,6 @@ def _net(dims, seed):
     return [torch.nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1)]
 
 
-def _f64_pass(lin, x, gy):
-    """float64 forward / backward by hand: Y, the gradients and every entry's absolute sum S"""
-    Ws = [l.weight.detach().double() for l in lin]
-    bs = [l.bias.detach().double() for l in lin]
-    H, Z = [x.double()], []
-    for i, (W, b) in enumerate(zip(Ws, bs)):
-        z = H[-1] @ W.t() + b
-        Z.append(z)
-        if i < len(Ws) - 1:
-            H.append(torch.nn.functional.gelu(z))
-    y = Z[-1]
-    SY = H[-1].abs() @ Ws[-1].abs().t() + bs[-1].abs()
-    dz = gy.double()
-    grads, sums = {}, {}
-    for l in range(len(Ws) - 1, -1, -1):
-        grads["dW%d" % (l + 1)] = dz.t() @ H[l]
-        sums["dW%d" % (l + 1)] = dz.abs().t() @ H[l].abs()
-        grads["db%d" % (l + 1)] = dz.sum(0)
-        sums["db%d" % (l + 1)] = dz.abs().sum(0)
-        dh = dz @ Ws[l]
-        if l == 0:
-            grads["dX"] = dh
-            sums["dX"] = dz.abs() @ Ws[l].abs()
-        else:
-            zz = Z[l - 1]
-            gp = 0.5 * (1 + torch.erf(zz / 2 ** 0.5)) + zz * torch.exp(-0.5 * zz * zz) / (2 * torch.pi) ** 0.5
-            dz = dh * gp
-    return y, SY, grads, sums
-
-
-def _per_entry(got, ref, S):
-    d = (got.double() - ref).abs()
-    bad_zero = bool(((S == 0) & (d != 0)).any())
-    e = torch.where(S > 0, d / S.clamp_min(1e-300), torch.zeros_like(d))
-    return float(e.max()), bad_zero
-
-
 # (net, N, scale of the lattice features: 1e-5 at initialisation, 1e-2 trained; the colour head has no lattice-feature input)
 CASES = [(d, n, s) for d, n in ((COLOUR, 49_152), (COLOUR, 30_001), (DENSITY, 49_152), (DENSITY, 23_001)) for s in (1e-5, 1e-2)] + \
         [(HEAD, 22_753, 1e-5)]
@@ -124,7 +89,7 @@ def test_wide_split_f16_per_entry_against_float64(dev, dims, N, lattice, dy, mon
     gy = torch.randn(N, dims[-1], generator=gen)
     if dy == "six_decades":         # NeuS weights: per-sample magnitudes spread over six decades within a batch
         gy = gy * 10.0 ** (-6.0 * torch.rand(N, 1, generator=gen))
-    y64, SY, g64, s64 = _f64_pass(lin, x, gy)
+    y64, SY, g64, s64, _ = _f64_pass(lin, x, gy)
     # torch fp32 on the same metric
     net32 = [l.to(dev) for l in lin]
     x32 = x.to(dev).requires_grad_(True)
