@@ -100,6 +100,9 @@ __device__ __forceinline__ float gelu_rational(float z) {
 // MFMAs per tile where the bf16 one issues 156, so it is bound by the NUMBER of VALU instructions rather than by what hides
 // beside the matrix pipe -- 9.5 instead of 14 instructions per element.  Same operations in the same order, fused where the
 // scalar form is fused: bit-identical results.  |z| rides as a source modifier of the scalar fmas that need it.
+// At four waves per SIMD (mlp_fwd_split_wg_kernel) the forward is bound by vector-ALU issue and the shorter tail below pays:
+// 0.2691 -> 0.2495 ms for the forward of the bench step with the tail and the build flag alone, 0.2460 with the operand
+// trims of mlp.hip / mlp_device.h (profiles/mlp_fwd_issue_trims_ab.txt); at two waves per SIMD it had measured neutral.
 __device__ __forceinline__ f32x2 gelu_rational2(f32x2 z) {
   const f32x2 e = (z * z) * f32x2{-0.72134752044448170368f, -0.72134752044448170368f};
   const f32x2 E = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
@@ -109,7 +112,13 @@ __device__ __forceinline__ f32x2 gelu_rational2(f32x2 z) {
   PSDF_H2(-2.582434118e-01f) PSDF_H2(3.751679361e-01f) PSDF_H2(-1.663514599e-02f) PSDF_H2(1.944366544e-01f) PSDF_H2(1.514270604e-01f)
 #undef PSDF_H2
   const f32x2 tail = (q * t) * E;
-  return f32x2{fmaf(-fabsf(z.x), tail.x, fmaxf(z.x, 0.f)), fmaf(-fabsf(z.y), tail.y, fmaxf(z.y, 0.f))};
+  // the tail, one element per instruction on purpose: max(z, 0) as v_med3_f32 z, 0, FLT_MAX (fmaxf is TWO v_max_f32, a
+  // canonicalisation first; with +inf as the bound the compiler folds the median back into that pair) and -|z| as the source
+  // modifiers of a scalar v_fma_f32 (v_pk_fma_f32 takes no |.|: packed, -|z| costs a v_or_b32 per element -- which is what the
+  // SLP vectoriser makes of the two fmas, so the forwards' file is built with -fno-slp-vectorize, build.py).  Same values for
+  // every finite z; three instructions per pair shorter.
+  const float mx = __builtin_amdgcn_fmed3f(z.x, 0.f, __FLT_MAX__), my = __builtin_amdgcn_fmed3f(z.y, 0.f, __FLT_MAX__);
+  return f32x2{__builtin_fmaf(-__builtin_fabsf(z.x), tail.x, mx), __builtin_fmaf(-__builtin_fabsf(z.y), tail.y, my)};
 }
 
 // ------------------------------------------------------------ value and derivative (the backwards' recompute)

@@ -15,6 +15,7 @@
 // The first layer reads its B operand straight from the feature-major encoding output [K0, N]
 // (two 128-B segments per wave load); the result is stored feature-major [OUT, N].
 #include "psdf_common.h"
+#include <type_traits>
 
 #include "mlp_device.h"
 #include "mlp_dispatch.h"
@@ -223,18 +224,73 @@ __global__ void __launch_bounds__(PSDF_BLOCK, 2)
     if constexpr (F16) apply_gelu_packed<T_>(H_); \
     else apply_gelu_scalar<T_>(H_);               \
   } while (0)
-// W: waves of the workgroup, which share ONE weight image (the image, not the registers, is what limits the residency of the
-// 64-wide nets: see SPLIT_LDS_MAX in mlp_device.h).  Wave w of workgroup b walks the tiles b W + w, + gridDim.x W, ...
-template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16, int W>
-__device__ __forceinline__ void mlp_fwd_split_body(const MlpPlan& p, const SplitPlan& sp, int64_t N, const float* __restrict__ X,
-                                                   const float* __restrict__ packed, const unsigned char* __restrict__ skip,
-                                                   float* __restrict__ Y) {
-  extern __shared__ __align__(16) u32x4 simg[];
-  {
-    const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(packed + sp.base);
-    for (int i = threadIdx.x; i < sp.total_rec; i += W * 64) simg[i] = src[i];
+// O32: how a lane addresses its layer-0 operands X[row][column].  The row bases X + row N are wave-uniform and stay on the scalar
+// unit in both forms; with O32 a load is scalar base + ONE 32-bit per-lane byte offset (global_load_dword v, v_off, s[base:base+1]),
+// computed once per tile: the lane's column, plus the h-half's eight rows.  No vector ALU per load.  The largest offset is
+// 4 (N - 1) + 32 N, so the form is taken where 36 N fits 32 bits (x_offsets_fit32, per launch); beyond that the lane keeps two
+// 64-bit pointers and every load adds the scalar row offset to one of them (what the kernel did for every N before).
+__host__ __device__ inline bool x_offsets_fit32(int64_t N) { return (uint64_t)N * 36u <= 0xFFFFFFFFull; }
+
+typedef const __attribute__((address_space(1))) char* xrow_t;   // a row's address: global memory, so that a load stays global_load
+
+template <bool O32>
+struct XLane {
+  const float* __restrict__ X;   // uniform
+  int64_t N;                     // uniform
+  uint32_t v0, vh;               // O32: byte offset of the column; the same plus eight rows for the lanes of half 1
+  const float* p0;               // !O32: the same two as pointers
+  const float* ph;
+  __device__ __forceinline__ XLane(const float* __restrict__ X_, int64_t N_, int64_t nc, int h) : X(X_), N(N_) {
+    if constexpr (O32) {
+      v0 = (uint32_t)nc * 4u;
+      vh = v0 + (h ? (uint32_t)N * 32u : 0u);
+      p0 = ph = nullptr;
+    } else {
+      v0 = vh = 0;
+      p0 = X + nc;
+      ph = p0 + (h ? (int64_t)8 * N : (int64_t)0);
+    }
   }
-  __syncthreads();
+  // A row as a wave-uniform cursor: the address of X[row][0] (O32) or its element offset row N; next() steps one row down.
+  using Row = std::conditional_t<O32, xrow_t, int64_t>;
+  __device__ __forceinline__ Row row(int r) const {
+    if constexpr (O32) return (xrow_t)(X + (int64_t)r * N);
+    else return (int64_t)r * N;
+  }
+  __device__ __forceinline__ Row next(Row r, bool step = true) const {
+    if constexpr (O32) return r + (step ? N * 4 : (int64_t)0);
+    else return r + (step ? N : (int64_t)0);
+  }
+  // The lane's column: half = false: X[row][column] in every lane; true: X[row + 8 h][column].  Asked for once per k-step, in the
+  // block of its loads: the empty asm makes the 32-bit offset a value of THAT block, so that instruction selection sees
+  // scalar base + zero-extended offset and takes the scalar-base form of the load (hoisted out of the block, the extension
+  // arrives as a 64-bit vector register and every load gets a 64-bit vector add again).  At most one v_mov_b32 per k-step.
+  using Col = std::conditional_t<O32, uint32_t, const float*>;
+  __device__ __forceinline__ Col col(bool half) const {
+    if constexpr (O32) {
+      uint32_t o = half ? vh : v0;
+      asm("" : "+v"(o));
+      return o;
+    } else {
+      return half ? ph : p0;
+    }
+  }
+  // The empty asm pins the row address to a scalar register pair the optimiser cannot see through: left alone it re-associates
+  // (X + lane offset) + row offset, the 64-bit vector add per load.
+  __device__ __forceinline__ float load(Row r, Col c) const {
+    if constexpr (O32) {
+      asm("" : "+s"(r));
+      return *(const __attribute__((address_space(1))) float*)(r + c);
+    } else {
+      return c[r];
+    }
+  }
+};
+
+template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16, int W, bool O32>
+__device__ __forceinline__ void mlp_fwd_split_tiles(const MlpPlan& p, const SplitPlan& sp, int64_t N, const float* __restrict__ X,
+                                                    const unsigned char* __restrict__ skip, float* __restrict__ Y) {
+  extern __shared__ __align__(16) u32x4 simg[];
   const float* tail = reinterpret_cast<const float*>(simg + sp.tail_rec);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (scalar: the tile loop is uniform)
   const int h = lane >> 5, sl = lane & 31;
@@ -250,21 +306,34 @@ __device__ __forceinline__ void mlp_fwd_split_body(const MlpPlan& p, const Split
     // ---- layer 0: lane (n, h) reads features 16 s + 8 h + j; CH k-steps of loads in flight before their MFMAs
     f32x16 h1[T1];
     init_bias4<T1>(h1, tail + sp.b_off[0], h);
-    const float* __restrict__ xl = X + nc + (h ? (int64_t)8 * N : (int64_t)0);  // this lane's column, rows 8 h + ...
+    const XLane<O32> xl(X, N, nc, h);
     for (int s0 = 0; s0 < ns0; s0 += CH) {
       float xs[CH][8];
 #pragma unroll
       for (int i = 0; i < CH; i++) {
         const int sb = 16 * (s0 + i);  // wave-uniform
-        if (sb + 16 <= K0) {           // whole k-step inside the input: row offsets are scalar, no guards
+        const int rem = K0 - sb;       // rows of this k-step inside the input (wave-uniform)
+        if (rem >= 16) {               // whole k-step: rows sb + 8 h + j
+          auto r = xl.row(sb);
+          const auto c = xl.col(true);
 #pragma unroll
-          for (int j = 0; j < 8; j++) xs[i][j] = xl[(int64_t)(sb + j) * N];
-        } else if (sb < K0) {          // the partial last k-step: clamped address + select (no exec-mask branch per load)
+          for (int j = 0; j < 8; j++, r = xl.next(r)) xs[i][j] = xl.load(r, c);
+        } else if (rem > 8) {          // partial, both halves: half 0 whole, half 1 has rows sb + 8 + j for j < rem - 8
+          auto r = xl.row(sb);
+          const auto c0 = xl.col(false), ch = xl.col(true);
 #pragma unroll
-          for (int j = 0; j < 8; j++) {
-            const int k = sb + 8 * h + j;
-            const float v = X[(int64_t)(k < K0 ? k : K0 - 1) * N + nc];
-            xs[i][j] = k < K0 ? v : 0.f;
+          for (int j = 0; j < 8; j++, r = xl.next(r)) {
+            const bool both = 8 + j < rem;                    // uniform
+            const float v = xl.load(r, both ? ch : c0);       // where half 1 has no row it reads half 0's (inside the input)
+            xs[i][j] = (both || h == 0) ? v : 0.f;
+          }
+        } else if (rem > 0) {          // partial, half 0 alone: rows sb + j for j < rem; every lane reads a row inside the input
+          auto r = xl.row(sb);
+          const auto c = xl.col(false);
+#pragma unroll
+          for (int j = 0; j < 8; j++, r = xl.next(r, j < rem)) {   // (the cursor stops on the last row)
+            const float v = xl.load(r, c);
+            xs[i][j] = (j < rem && h == 0) ? v : 0.f;
           }
         } else {
 #pragma unroll
@@ -322,6 +391,23 @@ __device__ __forceinline__ void mlp_fwd_split_body(const MlpPlan& p, const Split
       }
     }
   }
+}
+
+// W: waves of the workgroup, which share ONE weight image (the image, not the registers, is what limits the residency of the
+// 64-wide nets: see SPLIT_LDS_MAX in mlp_device.h).  Wave w of workgroup b walks the tiles b W + w, + gridDim.x W, ...
+template <int T1, int T2, int T3, int OUT_T, bool FINAL_DOT, int CH, bool F16, int W>
+__device__ __forceinline__ void mlp_fwd_split_body(const MlpPlan& p, const SplitPlan& sp, int64_t N, const float* __restrict__ X,
+                                                   const float* __restrict__ packed, const unsigned char* __restrict__ skip,
+                                                   float* __restrict__ Y) {
+  extern __shared__ __align__(16) u32x4 simg[];
+  {
+    const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(packed + sp.base);
+    for (int i = threadIdx.x; i < sp.total_rec; i += W * 64) simg[i] = src[i];
+  }
+  __syncthreads();
+  // one uniform branch per launch (the kernels' signatures and instantiations stay what the dispatch and resource tests pin)
+  if (x_offsets_fit32(N)) mlp_fwd_split_tiles<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16, W, true>(p, sp, N, X, skip, Y);
+  else mlp_fwd_split_tiles<T1, T2, T3, OUT_T, FINAL_DOT, CH, F16, W, false>(p, sp, N, X, skip, Y);
 }
 
 // The four-wave form: every net of the SPLIT column, every batch size.
@@ -422,7 +508,7 @@ int launch_fwd_split_wide(const MlpPlan& p, const SplitPlan& sp, int64_t N, cons
 // Launch policy.  The wide form is taken when every CU gets a full resident round of it, 16 tiles (two 8-wave workgroups);
 // below that the four-wave form spreads a small batch (a training step's 49 K samples: 1536 tiles) over all CUs.  Measured on
 // MI355X (256 CUs), us per launch, median of 15, forced forms (profiles/mlp_fwd_forms_ab.txt has the other nets; W = 16 was
-// built for the measurement, and the build also had a GELU tail three instructions per pair shorter that is not in the library):
+// built for the measurement; the build had the shorter GELU tail the library has again since the operand trims, not these):
 //                      36-64-64-64-1, fp16 pieces        36-64-64-64-1, bf16 pieces
 //     N   tiles / CU    W = 4    W = 8   W = 16           W = 4    W = 8   W = 16
 //    49 152      6       15.8     15.0     20.2            17.3     18.0     22.3

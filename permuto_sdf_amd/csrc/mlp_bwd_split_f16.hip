@@ -75,8 +75,8 @@ struct BP {  // the two fp16 pieces of one 8-element operand: p[0] = high, p[1] 
 // hazard recogniser must see the VALU write -- an MFMA that reads a register needs two wait states after a VALU wrote it (the
 // compiler puts an s_nop 1 there), and a build with the instruction in an asm statement computed garbage whenever the
 // scheduler happened to place one directly in front of an MFMA.
-// (One of three two-piece splits kept apart on purpose: wsplit2 in mlp_wide.hip is the subtract-and-convert form on a pair,
-// split8h in mlp_device.h the same on eight values; same pieces, different instructions.)
+// (split8h in mlp_device.h is this split on eight values, for the forwards; wsplit2 in mlp_wide.hip is kept apart on purpose:
+// the subtract-and-convert form on a pair, in a file built WITH the SLP vectoriser.  Same pieces, different instructions.)
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
   float one = 1.0f;
   asm("" : "+s"(one));

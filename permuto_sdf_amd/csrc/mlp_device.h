@@ -236,15 +236,26 @@ __device__ __forceinline__ void init_bias4(f32x16 (&acc)[T], const float* __rest
 // Half the MFMAs and about half the splitting work of the three-piece bf16 scheme; gfx950's matrix pipe honours fp16 subnormals
 // (attic/prototypes/mlp_fwd_split_f16.hip), so small low pieces keep an absolute precision of 2^-24; values must stay below 65504.
 // The image keeps the three-slot record layout (slot 2 unused), so SplitPlan is shared.
-// (One of three two-piece splits kept apart on purpose: split2 in mlp_bwd_split_f16.hip is the fma-mix form and needs
-// -fno-slp-vectorize, wsplit2 in mlp_wide.hip the subtract-and-convert form on a pair; same pieces, different instructions.)
+// The low piece is fp16(fma(x, 1, -high)): v_fma_mixlo_f16 / v_fma_mixhi_f16 form x - high exactly and round it once, ONE
+// instruction per element -- v_cvt_pk_f16_f32 + two fma-mix = three instructions per pair, where converting the high pieces
+// back, a packed subtraction and a second packed conversion take five.  x - high is exact in fp32 either way, so the pieces are
+// the same bits (tests/test_split_f16_numerics.py states the rounding).  `one` is 1.0f the optimiser cannot see through, and
+// the file must be built with -fno-slp-vectorize (build.py: mlp.hip), both for the reasons given at split2 in
+// mlp_bwd_split_f16.hip, which is this split on a pair.  Measured at four waves per SIMD, where the forward is bound by
+// vector-ALU issue: profiles/mlp_fwd_issue_trims_ab.txt (at two waves per SIMD round 4 had measured it neutral).
+// (Two forms of the two-piece split remain: this fma-mix form in the forwards here and in split2 of mlp_bwd_split_f16.hip,
+// both in files built without the SLP vectoriser, and wsplit2 in mlp_wide.hip, the subtract-and-convert form on a pair in a
+// file built with it; same pieces, different instructions.)
 __device__ __forceinline__ void split8h(const float (&x)[8], f16x8& hi, f16x8& lo) {
   u32x4 qh, ql;
+  float one = 1.0f;
+  asm("" : "+s"(one));
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const h2v_t h2 = __builtin_convertvector(f32x2{x[2 * i], x[2 * i + 1]}, h2v_t);   // v_cvt_pk_f16_f32, nearest even
-    const f32x2 r = f32x2{x[2 * i], x[2 * i + 1]} - f32x2{(float)h2[0], (float)h2[1]};      // exact
-    const h2v_t l2 = __builtin_convertvector(r, h2v_t);
+    h2v_t l2;
+    l2[0] = (_Float16)__builtin_fmaf(x[2 * i], one, -(float)h2[0]);
+    l2[1] = (_Float16)__builtin_fmaf(x[2 * i + 1], one, -(float)h2[1]);
     qh[i] = __builtin_bit_cast(uint32_t, h2);
     ql[i] = __builtin_bit_cast(uint32_t, l2);
   }

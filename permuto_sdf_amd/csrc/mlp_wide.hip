@@ -557,9 +557,9 @@ int wide_forward(const int* dims, int64_t N, const float* X, const float* const*
 // Same gradient image, same summing launch as the fp32 kernel.  Accuracy: tests/test_gpu_mlp.py::test_wide_net_backward_*.
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #define MFMA16H(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-// two fp32 -> packed high pieces, packed low pieces (element 0 in the low half).  (One of three two-piece splits kept apart on
-// purpose: split2 in mlp_bwd_split_f16.hip is the fma-mix form and needs -fno-slp-vectorize, split8h in mlp_device.h works on
-// eight values; same pieces, different instructions.)
+// two fp32 -> packed high pieces, packed low pieces (element 0 in the low half).  (The subtract-and-convert form, kept apart on
+// purpose: split2 in mlp_bwd_split_f16.hip and split8h in mlp_device.h are the fma-mix form and need -fno-slp-vectorize, which
+// this file is not built with; same pieces, different instructions.)
 __device__ __forceinline__ void wsplit2(float x0, float x1, uint32_t& hi, uint32_t& lo) {
   const h2v_t h = __builtin_convertvector(f32x2{x0, x1}, h2v_t);      // v_cvt_pk_f16_f32: nearest even
   const f32x2 r = f32x2{x0, x1} - f32x2{(float)h[0], (float)h[1]};   // exact
