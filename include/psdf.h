@@ -36,6 +36,12 @@ extern "C" {
 int64_t psdf_encode_convention(int which);
 int psdf_encode_set_conventions(uint32_t hash_multiplier, int rank_tie_raises_later);
 
+/* The launch form of the encode forward for this process: a grid row per level (0), or coarse levels handled together with
+   fine ones, `pairs` of them (n > 0, clamped to nr_levels / 2 per call; -1: the library's default rule, also what
+   PSDF_ENC_FWD_PAIRS sets at start-up).  A speed setting only: the outputs are bit-identical in every form.  -1 (argument
+   error) below -1.  No reference counterpart. */
+int psdf_encode_set_forward_pairs(int pairs);
+
 /* replaces: permutohedral_encoding CUDA op `forward_gpu` (un-vendored; call sites permuto_sdf_py/models/models.py:186,370,500,542)
    -2 (unsupported) when one level of the table exceeds 4 GiB (capacity * nr_feat * 4 bytes: the kernel gathers with 32-bit
    offsets from the level's base; the reference's tables are 2 MiB per level) */

@@ -9,9 +9,13 @@
 //   sliced         [Lt*F, N]   fp32 feature-major (Lt = L + ceil(P/F) when points are concatenated):
 //                              every store of a wave is one 256-B line, and the consumer (the fused MLP,
 //                              mlp.hip) reads its MFMA B-operand rows straight from this layout.
-// Launch shape: grid (ceil(N/256), Lt), one thread per (point, level).  blockIdx.x is the fast dispatch
-// dimension, so the chip sweeps one level's 2-MiB table at a time and that table stays resident in every
-// XCD's 4-MiB L2 (the gathers are L2 hits, HBM sees positions + outputs only).
+// Launch shape of the forward: grid (one resident round of workgroups, slots).  A slot is a coarse level together with a fine
+// one -- slot i holds levels i and L - 1 - i, a thread computes both for its point (encode_fwd_pair_kernel; the plan is
+// forward_slots of encode_plan.h) -- or a single level: the middle level of an odd L, the pseudo-levels, every level when
+// pairing is off (PSDF_ENC_FWD_PAIRS=0 / psdf_encode_set_forward_pairs(0): encode_fwd_kernel, grid (.., Lt), one thread per
+// (point, level)).  blockIdx.x is the fast dispatch dimension, so the chip sweeps one slot at a time: the fine level's 2-MiB
+// table stays resident in every XCD's 4-MiB L2 (the gathers are L2 hits, HBM sees positions + outputs only) and the coarse
+// level beside it reads a few dozen to a few thousand rows of its own.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -24,6 +28,112 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------ forward
+// What the per-(point, level) body needs besides the point: the kernels' arguments, bundled inside the kernel (the compiler
+// dissolves the struct: every member stays the scalar register it was).
+struct FwdArgs {
+  int64_t N;
+  int L;
+  uint32_t capacity;
+  EncConv conv;
+  const float *lattice, *scale_factor, *shifts, *window;
+  float points_scaling;
+  int pad_points;
+  float* sliced;
+  unsigned char* touched;
+  int touch_shift, blocks_per_level;
+};
+
+// One (point, level) between its gathers and its weighted sum: the P+1 table rows as loaded and their weights bary_r * window.
+template <int P, int F>
+struct FwdGather {
+  float fv[P + 1][F];
+  float bw[P + 1];
+};
+
+// The levels without gathers (workgroup-uniform): true when `level` was one of them and its rows are written.
+template <int P, int F>
+__device__ __forceinline__ bool fwd_level_flat(const FwdArgs& A, int level, int64_t n, const float (&pos)[P]) {
+  if (level >= A.L) {  // pseudo-levels carrying the scaled input point (zero padded)
+    const int e = level - A.L;
+#pragma unroll
+    for (int f = 0; f < F; f++) {
+      const int d = e * F + f;
+      float v = 0.f;
+#pragma unroll
+      for (int i = 0; i < P; i++)
+        if (i == d) v = pos[i] * A.points_scaling;
+      // channel L*F + d; d >= P exists only in the zero-padded pseudo-level layout (encode_conventions.h)
+      if (d < P || A.pad_points) A.sliced[((int64_t)level * F + f) * A.N + n] = v;
+    }
+    return true;
+  }
+  if (A.window[level] == 0.f) {  // a level the coarse-to-fine window keeps closed (workgroup-uniform): its channels are
+                                 // 0 * (finite rows) = 0, no simplex, no gathers, nothing to mark (its backward contributes nothing either)
+#pragma unroll
+    for (int f = 0; f < F; f++) A.sliced[((int64_t)level * F + f) * A.N + n] = 0.f;
+    return true;
+  }
+  return false;
+}
+
+// An open lattice level, first half: locate the simplex, mark the touched blocks, ISSUE all P+1 gathers.  fwd_level_finish
+// consumes them; a caller may start a second level in between.
+template <int P, int F, bool PLAIN>
+__device__ __forceinline__ void fwd_level_gather(const FwdArgs& A, int level, int64_t n, const float (&pos)[P], FwdGather<P, F>& g) {
+  const float w = A.window[level];
+  Simplex<P> s;
+  compute_simplex<P>(pos, A.shifts + level * P, A.scale_factor + level * P, s, A.conv.tie_later);
+  const float* __restrict__ table = A.lattice + (int64_t)level * A.capacity * F;
+  // issue all P+1 gathers before consuming them (independent 8-B loads in flight)
+  uint32_t row[P + 1];
+  vertex_rows<P>(s, A.capacity, row, A.conv.hash_c);
+  // Training forward: remember which blocks of table rows this batch reads.  Every lattice-gradient contribution of the
+  // backward / double backward at these positions lands on exactly these rows, so the optimiser can skip blocks whose
+  // gradient and moments are still exactly zero (optim.hip: adamw_blocks_kernel) -- a superset is all it needs.
+  if (!PLAIN && A.touched) {
+#pragma unroll
+    for (int r = 0; r <= P; r++) A.touched[(int64_t)level * A.blocks_per_level + (row[r] >> A.touch_shift)] = 1;
+  }
+#pragma unroll
+  for (int r = 0; r <= P; r++) {
+    // 32-bit byte offset from the level's table (a wave-uniform base): one shift per gather instead of a 64-bit shift-add
+    // (a level of the table is below 4 GiB: checked by the launcher)
+    const char* tb = reinterpret_cast<const char*>(table);
+    if (F == 2) {
+      float2 t = *reinterpret_cast<const float2*>(tb + (row[r] * 8u));
+      g.fv[r][0] = t.x;
+      g.fv[r][F - 1] = t.y;
+    } else {
+#pragma unroll
+      for (int f = 0; f < F; f++) g.fv[r][f] = *reinterpret_cast<const float*>(tb + (row[r] * (uint32_t)(F * 4) + (uint32_t)(f * 4)));
+    }
+  }
+#pragma unroll
+  for (int r = 0; r <= P; r++) g.bw[r] = s.bary[r] * w;
+}
+
+// Second half: the weighted sum of the gathered rows, and the level's F output rows.
+template <int P, int F>
+__device__ __forceinline__ void fwd_level_finish(const FwdArgs& A, int level, int64_t n, const FwdGather<P, F>& g) {
+  float acc[F];
+#pragma unroll
+  for (int r = 0; r <= P; r++) {
+#pragma unroll
+    for (int f = 0; f < F; f++) acc[f] = r == 0 ? g.fv[r][f] * g.bw[r] : acc[f] + g.fv[r][f] * g.bw[r];   // (0 + x: the sign of a zero only)
+  }
+#pragma unroll
+  for (int f = 0; f < F; f++) A.sliced[((int64_t)level * F + f) * A.N + n] = acc[f];
+}
+
+// The whole body of one (point, level): what encode_fwd_kernel does per thread, and the pair kernel for a slot's only level.
+template <int P, int F, bool PLAIN>
+__device__ __forceinline__ void fwd_level(const FwdArgs& A, int level, int64_t n, const float (&pos)[P]) {
+  if (fwd_level_flat<P, F>(A, level, n, pos)) return;
+  FwdGather<P, F> g;
+  fwd_level_gather<P, F, PLAIN>(A, level, n, pos, g);
+  fwd_level_finish<P, F>(A, level, n, g);
+}
+
 template <int P, int F, bool PLAIN = false>   // PLAIN: no skip mask, no touched-block map (their arguments are ignored)
 __global__ void __launch_bounds__(PSDF_BLOCK)
     encode_fwd_kernel(int64_t N, int L, uint32_t capacity, EncConv conv, const float* __restrict__ positions,
@@ -35,74 +145,93 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   // levels for ALL points so that a table is fetched into one L2 instead of eight: 0.358 -> 0.631 ms at 2 M points, 16 levels
   // (profiles/r04_enc_ab.jsonl).  Eight XCDs streaming eight different tables each touch every position and write every
   // output row with 1/8 of the chip; the level-at-a-time sweep below keeps all 256 CUs on one 2-MiB table.)
+  const FwdArgs A{N, L, capacity, conv, lattice, scale_factor, shifts, window, points_scaling, pad_points, sliced, touched,
+                  touch_shift, blocks_per_level};
   const int level = blockIdx.y;
   const int64_t ntiles = (N + PSDF_BLOCK - 1) / PSDF_BLOCK;
   // a workgroup walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... of its level (gridDim.x = the number of tiles unless the
   // launcher caps it: then the level's constants are fetched once per workgroup instead of once per tile)
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-  const int64_t n = tile * PSDF_BLOCK + threadIdx.x;
-  if (n >= N) continue;
-  if (!PLAIN && skip && skip[n]) continue;  // masked point (fixed-shape callers, e.g. converged rays): its columns stay untouched
-  float pos[P];
-  load_pos<P>(positions, n, pos);
-  if (level >= L) {  // pseudo-levels carrying the scaled input point (zero padded)
-    const int e = level - L;
-#pragma unroll
-    for (int f = 0; f < F; f++) {
-      const int d = e * F + f;
-      float v = 0.f;
-#pragma unroll
-      for (int i = 0; i < P; i++)
-        if (i == d) v = pos[i] * points_scaling;
-      // channel L*F + d; d >= P exists only in the zero-padded pseudo-level layout (encode_conventions.h)
-      if (d < P || pad_points) sliced[((int64_t)level * F + f) * N + n] = v;
+    const int64_t n = tile * PSDF_BLOCK + threadIdx.x;
+    if (n >= N) continue;
+    if (!PLAIN && skip && skip[n]) continue;  // masked point (fixed-shape callers, e.g. converged rays): its columns stay untouched
+    float pos[P];
+    load_pos<P>(positions, n, pos);
+    fwd_level<P, F, PLAIN>(A, level, n, pos);
+  }
+}
+
+// A loop-invariant scalar, made opaque for one trip of the tile loop.  Left alone the compiler hoists everything derived from
+// such a value out of the loop -- a level's pointers into the constants, its table and its output rows, the powers of the hash
+// multiplier, every uniform condition as a 64-bit lane mask -- and holds it in scalar registers across the loop: with two levels
+// per thread that is more than the 102 a wave may have at 8 waves per SIMD (measured: 24 spilled in <3, 2, PLAIN>, 50 in the
+// general form).  Through this the derived values are recomputed per tile on the scalar unit, which has nothing else to do here.
+template <class T>
+__device__ __forceinline__ T per_tile(T v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
+// The same (point, level) bodies, two levels per thread: slot blockIdx.y of the plan names a level from the coarse end and one
+// from the fine end (encode_plan.h: forward_slots).  The position is loaded once, both simplices are located and all 2 (P+1)
+// gathers are issued before any is consumed -- the coarse level's gathers hit L1 and its time is vector issue, the fine level's
+// go to L2 and its time is waiting for them, so each fills the other's idle resource (profiles/enc_fwd_levels.txt).  Whether a
+// slot runs that way is decided once per workgroup: a slot with one level (the middle levels, the pseudo-levels), or with a level
+// that the window has closed, runs the plain body level after level.  Outputs are bit-identical to encode_fwd_kernel: the same
+// expressions per (point, level), no sum across levels.  One resident round of workgroups per slot walks the tiles, as there.
+template <int P, int F, bool PLAIN = false>
+__global__ void __launch_bounds__(PSDF_BLOCK)
+    encode_fwd_pair_kernel(int64_t N, int L, uint32_t capacity, EncConv conv, const float* __restrict__ positions,
+                           const float* __restrict__ lattice, const float* __restrict__ scale_factor,
+                           const float* __restrict__ shifts, const float* __restrict__ window, float points_scaling,
+                           int pad_points, const unsigned char* __restrict__ skip, float* __restrict__ sliced,
+                           unsigned char* __restrict__ touched, int touch_shift, int blocks_per_level,
+                           psdf::enc_plan::FwdSlots slots) {
+  const FwdArgs A{N, L, capacity, conv, lattice, scale_factor, shifts, window, points_scaling, pad_points, sliced, touched,
+                  touch_shift, blocks_per_level};
+  const int la = slots.a[blockIdx.y], lb = slots.b[blockIdx.y];   // lb == FWD_SLOT_NONE: a single level
+  const bool two = lb != psdf::enc_plan::FWD_SLOT_NONE;
+  const bool together = two && la < L && lb < L && window[la] != 0.f && window[lb] != 0.f;
+  const uint32_t ntiles = (uint32_t)((N + PSDF_BLOCK - 1) / PSDF_BLOCK);   // (32 bits: the launcher checks; three scalar registers)
+  if (together) {
+    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+      const int64_t n = (int64_t)tile * PSDF_BLOCK + threadIdx.x;
+      if (n >= N) continue;
+      if (!PLAIN) {   // masked point (fixed-shape callers, e.g. converged rays): its columns stay untouched
+        const unsigned char* sk = per_tile(skip);
+        if (sk && sk[n]) continue;
+      }
+      float pos[P];
+      load_pos<P>(positions, n, pos);
+      const int xa = per_tile(la), xb = per_tile(lb);
+      FwdArgs B = A;
+      B.capacity = per_tile(A.capacity);
+      B.conv.hash_c = per_tile(A.conv.hash_c);
+      B.conv.tie_later = per_tile(A.conv.tie_later);
+      if (!PLAIN) B.touched = per_tile(A.touched);
+      // (the coarse level first: 263.5 against 265.0 us with the fine one first, 2 M points x 16 levels, profiles/enc_fwd_pairs_ab.txt)
+      FwdGather<P, F> ga, gb;
+      fwd_level_gather<P, F, PLAIN>(B, xa, n, pos, ga);
+      fwd_level_gather<P, F, PLAIN>(B, xb, n, pos, gb);
+      fwd_level_finish<P, F>(A, xa, n, ga);
+      fwd_level_finish<P, F>(A, xb, n, gb);
     }
-    continue;
-  }
-  const float w = window[level];
-  if (w == 0.f) {  // a level the coarse-to-fine window keeps closed (workgroup-uniform): its channels are 0 * (finite rows) = 0,
-                   // no simplex, no gathers, nothing to mark (its backward contributes nothing either)
-#pragma unroll
-    for (int f = 0; f < F; f++) sliced[((int64_t)level * F + f) * N + n] = 0.f;
-    continue;
-  }
-  Simplex<P> s;
-  compute_simplex<P>(pos, shifts + level * P, scale_factor + level * P, s, conv.tie_later);
-  const float* __restrict__ table = lattice + (int64_t)level * capacity * F;
-  // issue all P+1 gathers before consuming them (independent 8-B loads in flight)
-  uint32_t row[P + 1];
-  vertex_rows<P>(s, capacity, row, conv.hash_c);
-  // Training forward: remember which blocks of table rows this batch reads.  Every lattice-gradient contribution of the
-  // backward / double backward at these positions lands on exactly these rows, so the optimiser can skip blocks whose
-  // gradient and moments are still exactly zero (optim.hip: adamw_blocks_kernel) -- a superset is all it needs.
-  if (!PLAIN && touched) {
-#pragma unroll
-    for (int r = 0; r <= P; r++) touched[(int64_t)level * blocks_per_level + (row[r] >> touch_shift)] = 1;
-  }
-  float fv[P + 1][F];
-#pragma unroll
-  for (int r = 0; r <= P; r++) {
-    // 32-bit byte offset from the level's table (a wave-uniform base): one shift per gather instead of a 64-bit shift-add
-    // (a level of the table is below 4 GiB: checked by the launcher)
-    const char* tb = reinterpret_cast<const char*>(table);
-    if (F == 2) {
-      float2 t = *reinterpret_cast<const float2*>(tb + (row[r] * 8u));
-      fv[r][0] = t.x;
-      fv[r][F - 1] = t.y;
-    } else {
-#pragma unroll
-      for (int f = 0; f < F; f++) fv[r][f] = *reinterpret_cast<const float*>(tb + (row[r] * (uint32_t)(F * 4) + (uint32_t)(f * 4)));
+  } else {
+    // level after level (a second one only where the window has closed a member of a pair): ONE copy of the plain body
+    for (int k = 0; k < (two ? 2 : 1); k++) {
+      const int level = k ? lb : la;
+      for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t n = (int64_t)tile * PSDF_BLOCK + threadIdx.x;
+        if (n >= N) continue;
+        if (!PLAIN) {
+          const unsigned char* sk = per_tile(skip);
+          if (sk && sk[n]) continue;
+        }
+        float pos[P];
+        load_pos<P>(positions, n, pos);
+        fwd_level<P, F, PLAIN>(A, per_tile(level), n, pos);
+      }
     }
-  }
-  float acc[F];
-#pragma unroll
-  for (int r = 0; r <= P; r++) {
-    const float bw = s.bary[r] * w;
-#pragma unroll
-    for (int f = 0; f < F; f++) acc[f] = r == 0 ? fv[r][f] * bw : acc[f] + fv[r][f] * bw;   // (0 + x: the sign of a zero only)
-  }
-#pragma unroll
-  for (int f = 0; f < F; f++) sliced[((int64_t)level * F + f) * N + n] = acc[f];
   }
 }
 
@@ -1138,15 +1267,30 @@ dim3 plain_grid(const EncCall& c) {
 }
 
 // ---------------------------------------------------------------------------------- forward
+// The paired form, process-wide: -1 the default rule (encode_plan.h: forward_pairs_default), 0 off (one level per grid row),
+// n > 0 that many pairs.  PSDF_ENC_FWD_PAIRS is read once; psdf_encode_set_forward_pairs() replaces it (tests, A/B in one process).
+int& fwd_pairs_setting() {
+  static int v = env_int("PSDF_ENC_FWD_PAIRS", -1);
+  return v;
+}
+
 template <int P, int F>
 int launch_fwd(int_c<P>, int_c<F>, const EncCall& c, dim3 grid, const unsigned char* skip, float* sliced, unsigned char* touched,
-               int touch_shift) {
+               int touch_shift, const plan::FwdSlots& slots) {
   const int touch_blocks = (c.capacity + (1 << touch_shift) - 1) >> touch_shift;
   // (without a mask and a touched-block map the kernel needs fewer scalar registers: 8 instead of 7 waves per SIMD)
-  if (!skip && !touched)
+  const bool plain = !skip && !touched;
+  if (slots.n > 0) {
+    grid.y = (unsigned)slots.n;
+    if (plain)
+      launch_enc(encode_fwd_pair_kernel<P, F, true>, grid, 0, c, c.pad, skip, sliced, touched, touch_shift, touch_blocks, slots);
+    else
+      launch_enc(encode_fwd_pair_kernel<P, F, false>, grid, 0, c, c.pad, skip, sliced, touched, touch_shift, touch_blocks, slots);
+  } else if (plain) {
     launch_enc(encode_fwd_kernel<P, F, true>, grid, 0, c, c.pad, skip, sliced, touched, touch_shift, touch_blocks);
-  else
+  } else {
     launch_enc(encode_fwd_kernel<P, F, false>, grid, 0, c, c.pad, skip, sliced, touched, touch_shift, touch_blocks);
+  }
   return PSDF_OK;
 }
 
@@ -1167,8 +1311,14 @@ int encode_forward_impl(int pos_dim, int nr_feat, int64_t N, int nr_levels, int 
   static const int fwd_env = env_int("PSDF_ENC_FWD_WGS", -1);
   const int fwd_wgs = fwd_env >= 0 ? fwd_env : device_cus() * 8;
   if (fwd_wgs > 0 && (int)grid.x > fwd_wgs) grid.x = fwd_wgs;
+  // grid rows: one per level, or one per slot of the paired form (a level from the coarse end with one from the fine end)
+  const int want = fwd_pairs_setting();
+  const int pairs = want < 0 ? plan::forward_pairs_default(nr_levels, N) : want;
+  // (the paired kernel counts its tiles in 32 bits: 2^40 points and more take the one-level form)
+  const bool pairable = pairs > 0 && (N + PSDF_BLOCK - 1) / PSDF_BLOCK <= 0xffffffffll;
+  const plan::FwdSlots slots = pairable ? plan::forward_slots(nr_levels, c.Lt, pairs) : plan::FwdSlots{};
   return launched(dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
-    return launch_fwd(p, f, c, grid, skip, sliced, touched, touch_shift);
+    return launch_fwd(p, f, c, grid, skip, sliced, touched, touch_shift, slots);
   }));
 }
 
@@ -1475,6 +1625,15 @@ int64_t psdf_encode_convention(int which) {
 int psdf_encode_set_conventions(uint32_t hash_multiplier, int rank_tie_raises_later) {
   if (hash_multiplier == 0u || (rank_tie_raises_later != 0 && rank_tie_raises_later != 1)) return PSDF_ERR_ARG;
   psdf::enc_conv_state() = EncConv{hash_multiplier, (uint32_t)rank_tie_raises_later};
+  return PSDF_OK;
+}
+
+// The paired form of the forward for this process (every later launch): -1 the default rule, 0 off (one level per grid row), n > 0
+// that many coarse-with-fine pairs (clamped to nr_levels / 2 per call).  Results do not depend on it.  Not thread-safe against
+// concurrent launches.
+int psdf_encode_set_forward_pairs(int pairs) {
+  if (pairs < -1) return PSDF_ERR_ARG;
+  fwd_pairs_setting() = pairs;
   return PSDF_OK;
 }
 

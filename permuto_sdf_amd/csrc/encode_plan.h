@@ -141,5 +141,51 @@ inline int deal_layout(std::vector<int>& counts, int cap, uint16_t* first) {
   return at;
 }
 
+// ------------------------------------------------------------------------------------------ forward slots
+// The paired forward (encode_fwd_pair_kernel) runs one grid row per SLOT: a slot names one level, or two that a thread handles
+// together.  Levels are taken as ordered coarse to fine by index (how every caller of this encoding builds its scale list; the
+// scale factors live in device memory, so the host cannot sort them -- the order affects speed only, never results): slot
+// i < pairs holds (i, L - 1 - i), one level from each end; the middle levels pairs .. L - 1 - pairs and the pseudo-levels
+// L .. Lt - 1 follow singly, in index order.  Passed to the kernel by value.
+constexpr int FWD_MAX_SLOTS = 42;
+constexpr uint8_t FWD_SLOT_NONE = 0xFF;
+struct FwdSlots {
+  int n;                      // slots = grid rows
+  uint8_t a[FWD_MAX_SLOTS];   // the slot's level (the coarse one of a pair)
+  uint8_t b[FWD_MAX_SLOTS];   // the fine level of a pair, or FWD_SLOT_NONE
+};
+
+// pairs is clamped to [0, L / 2].  n == 0: the plan does not apply (more than FWD_MAX_SLOTS slots, or a level index that does not
+// fit the table's bytes) and the caller launches one level per grid row as before.
+inline FwdSlots forward_slots(int L, int Lt, int pairs) {
+  FwdSlots s{};
+  if (L < 1 || Lt < L || Lt >= (int)FWD_SLOT_NONE) return s;
+  if (pairs < 0) pairs = 0;
+  if (pairs > L / 2) pairs = L / 2;
+  if (Lt - pairs > FWD_MAX_SLOTS) return s;
+  int at = 0;
+  for (int i = 0; i < pairs; i++, at++) {
+    s.a[at] = (uint8_t)i;
+    s.b[at] = (uint8_t)(L - 1 - i);
+  }
+  for (int l = pairs; l < Lt; l++) {
+    if (l < L && l >= L - pairs) continue;   // the fine member of a pair
+    s.a[at] = (uint8_t)l;
+    s.b[at] = FWD_SLOT_NONE;
+    at++;
+  }
+  s.n = at;
+  return s;
+}
+
+// How many levels to pair when nobody said (PSDF_ENC_FWD_PAIRS = -1): every level that has a partner, at every batch size.
+// Measured (profiles/enc_fwd_pairs_ab.txt), whole forward, pairs 0 / L/4 / 3L/8 / L/2: 2 M points x 16 levels 307.5 / 280.0 /
+// 268.5 / 264.3 us, x 24 levels 457.8 / 417.9 / 399.0 / 391.6 us -- the two half-hashed middle levels together still gain;
+// 49 152 points x 24 levels 25.8 / 24.5 / 23.1 / 23.2 us, 1 056 points inside the spread: no gate by N.
+inline int forward_pairs_default(int L, int64_t N) {
+  (void)N;
+  return L / 2;
+}
+
 }  // namespace enc_plan
 }  // namespace psdf
