@@ -396,6 +396,19 @@ int psdf_grid_update_with_sdf(int count, const int* voxel_indices, const float* 
 int psdf_grid_check_occupancy(int count, int nr_voxels_per_dim, float extent, const float* grid_translation, const
     uint8_t* grid_occupancy, const float* points, uint8_t* out, void* stream);
 
+/* replaces: the `weights` of run_net_sphere_traced (permuto_sdf_py/train_permuto_sdf.py:216-222: check_occupancy and
+   check_point_inside_primitive of the traced end points, times the rays that met occupancy at all) and the
+   compact_to_valid_samples behind it (src/RaySamplesPacked.cu:57-95).  A ray is valid iff no_hit [nr_rays] (1-byte bool) is 0,
+   its point lies in an occupied voxel (the lookup of psdf_grid_check_occupancy, out of range = empty) and
+   sqrtf((dx dx + dy dy) + dz dz) < sphere_radius for d = point - sphere_center (strict).  The valid rays are compacted IN RAY
+   ORDER, without atomics: slot [nr_rays] int32 <- the dense row of a valid ray, -1 otherwise; pos, dirs_out [>= M, 3] <- points
+   and dirs of the valid rays (rows from M on are not written); count [1] int32 <- M.  grid_translation, sphere_center: HOST
+   pointers to 3 floats.  scratch: 2 * ceil(nr_rays / 256) int32.  nr_rays = 0 returns 0 without a launch; -1 for nr_rays < 0 or
+   a NULL pointer. */
+int psdf_trace_frame_select(int nr_rays, int nr_voxels_per_dim, float extent, const float* grid_translation, const uint8_t*
+    grid_occupancy, float sphere_radius, const float* sphere_center, const float* points, const float* dirs, const uint8_t*
+    no_hit, int* scratch, int* slot, float* pos, float* dirs_out, int* count, void* stream);
+
 /* which form the last psdf_march_samples launched: 1 = march_kernel (a thread per ray), 2 = march_quad_kernel (four lanes per
    ray, unit grids with nr_rays <= 6144; PSDF_MARCH_FORM=thread|quad overrides); 0 = none yet.  Debug query (host only). */
 int psdf_march_form(void);
@@ -680,6 +693,23 @@ int psdf_image_ssim(const void* pred, int pred_u8, const int64_t* pred_strides, 
     gt_strides, const void* mask, int mask_u8, const int64_t* mask_strides, int64_t N, int C, int H, int W, double data_range,
     int kernel_size, double kernel_sigma, double k1, double k2, int downsample, double* workspace, double* out, double* map,
     void* stream);
+
+/* ---- frame_trace.hip ---- */
+/* replaces: what run_net_sphere_traced does after the networks (permuto_sdf_py/train_permuto_sdf.py:224-242: the integrals of
+   colour and SDF gradient with one sample per ray and a weight in {0, 1}, F.normalize, the weight sum, lin2nchw) and
+   rotate_normals_to_cam_frame (permuto_sdf_py/utils/common_utils.py:573-589) for the camera-frame normals, for the chunk
+   [pixel_first, pixel_first + nr_rays) of an H x W frame.  slot [nr_rays] from psdf_trace_frame_select; origins, dirs
+   [nr_rays, 3] the chunk's rays; pos, gradients, rgb [nr_valid, 3] the end points, SDF gradients and colours of the valid rays
+   (may be NULL with nr_valid = 0); rot_cam_world: device pointer to the 9 floats of the row-major rotation of tf_cam_world, read
+   when normals_cam_img is given.  Written at pixel pixel_first + ray, for a valid ray / any other: rgb_img [3, H, W] <- its rgb
+   row / 0; normals_img [3, H, W] <- g / max(|g|, 1e-12) / 0; normals_cam_img [3, H, W] or NULL <- normalize(R n) / 0;
+   weights_sum_img [1, H, W] <- 1 / 0; depth_img [1, H, W] <- ((px - ox) dx + (py - oy) dy) + (pz - oz) dz / 0 (not in the
+   reference).  One weight-1 sample per ray: colours and gradients are copied, not summed.  nr_rays = 0 returns 0 without a
+   launch; -1 for nr_rays < 0, nr_valid outside [0, nr_rays], a NULL pointer, an extent < 1 or a range outside the frame; -2 for
+   H W >= 2^31. */
+int psdf_trace_frame_resolve(int nr_rays, int nr_valid, const int* slot, const float* origins, const float* dirs, const float*
+    pos, const float* gradients, const float* rgb, const float* rot_cam_world, int H, int W, int64_t pixel_first, float* rgb_img,
+    float* normals_img, float* normals_cam_img, float* weights_sum_img, float* depth_img, void* stream);
 
 /* ---- frame_rays.hip, frame_composite.hip ---- */
 /* A held-out view rendered volumetrically, a chunk of pixels at a time, into planar [3, H, W] / [1, H, W] fp32 images on the

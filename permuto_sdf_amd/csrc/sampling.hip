@@ -1376,6 +1376,60 @@ __global__ void __launch_bounds__(1024)
   if (threadIdx.x == 0 && total_out) *total_out = carry_s;
 }
 
+// ---------------------------------------------------------------------------------- traced frame: the valid end points
+// The rays of a sphere-traced chunk that end on a surface point, compacted in RAY ORDER (run_net_sphere_traced,
+// permuto_sdf_py/train_permuto_sdf.py:216-222, and the compact_to_valid_samples behind it): a ray is valid iff it met an
+// occupied voxel at all, its end point lies in an occupied voxel (check_occupancy_kernel's lookup: out of range counts as
+// empty) and strictly inside the bounding sphere (Sphere::check_point_inside_primitive: |p - c| < radius).  Three launches, no
+// atomics and no block that waits for another: (1) the predicate, kept as 0 / -1 in slot[], and its count per workgroup -- a
+// 64-bit ballot and a population count per wave, the four wave counts added by thread 0; (2) scan_i32_kernel over the workgroup
+// counts, whose total is M; (3) the scatter: rank inside the wave from the ballot, plus the waves before, plus the workgroups
+// before.  HBM traffic per ray: (1) reads 12 B of end point, 1 B of no_hit and the 1-byte grid probe and writes 4 B; (3) reads
+// and writes those 4 B and moves 24 B in and 24 B out per valid ray (end point and direction).
+__global__ void __launch_bounds__(PSDF_BLOCK)
+    trace_select_count_kernel(int nr_rays, Grid g, const uint8_t* __restrict__ occ, float radius, float cx, float cy, float cz,
+                              const float* __restrict__ pts, const uint8_t* __restrict__ no_hit, int* __restrict__ slot,
+                              int* __restrict__ block_counts) {
+  __shared__ int wave_count[PSDF_BLOCK / 64];
+  const int i = blockIdx.x * PSDF_BLOCK + threadIdx.x;
+  bool valid = false;
+  if (i < nr_rays) {
+    if (!no_hit[i]) {
+      const v3 p = ld3(pts + 3 * (int64_t)i);
+      const int vox = g.pos_to_idx(p);
+      const v3 q = p - mk3(cx, cy, cz);
+      valid = (g.in_range(vox) ? occ[vox] : 0) != 0 && sqrtf(dot3(q, q)) < radius;
+    }
+    slot[i] = valid ? 0 : -1;
+  }
+  const unsigned long long votes = __ballot(valid);
+  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = __popcll(votes);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int n = 0;
+    for (int w = 0; w < PSDF_BLOCK / 64; w++) n += wave_count[w];
+    block_counts[blockIdx.x] = n;
+  }
+}
+__global__ void __launch_bounds__(PSDF_BLOCK)
+    trace_select_scatter_kernel(int nr_rays, const int* __restrict__ block_offsets, const float* __restrict__ pts,
+                                const float* __restrict__ dirs, int* __restrict__ slot, float* __restrict__ o_pos,
+                                float* __restrict__ o_dirs) {
+  __shared__ int wave_count[PSDF_BLOCK / 64];
+  const int i = blockIdx.x * PSDF_BLOCK + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool valid = i < nr_rays && slot[i] == 0;
+  const unsigned long long votes = __ballot(valid);
+  if (lane == 0) wave_count[wave] = __popcll(votes);
+  __syncthreads();
+  if (!valid) return;                       // (slot[i] already holds -1)
+  int dst = block_offsets[blockIdx.x] + __popcll(votes & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave; w++) dst += wave_count[w];
+  slot[i] = dst;
+  st3(o_pos + 3 * (int64_t)dst, ld3(pts + 3 * (int64_t)i));
+  st3(o_dirs + 3 * (int64_t)dst, ld3(dirs + 3 * (int64_t)i));
+}
+
 inline Grid mk_grid(int n, float extent, const float* tr) {
   const bool pow2 = n > 0 && (n & (n - 1)) == 0;
   return Grid{n, extent, tr[0], tr[1], tr[2], pow2 ? 1.0f / (float)n : 0.f, extent == 1.0f ? 1 : 0};
@@ -1448,6 +1502,30 @@ int psdf_grid_check_occupancy(int count, int nr_voxels_per_dim, float extent, co
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(check_occupancy_kernel, GRID1(count), count, mk_grid(nr_voxels_per_dim, extent, grid_translation),
                      grid_occupancy, points, out);
+  PSDF_LAUNCH_CHECK();
+  return PSDF_OK;
+}
+
+// The valid end points of a traced chunk, compacted in ray order (trace_select_count_kernel).  sphere_center: HOST pointer to 3
+// floats.  scratch: 2 * ceil(nr_rays / 256) ints.  slot [nr_rays] <- dense row of a valid ray, -1 otherwise; pos, dirs_out
+// [>= M, 3] <- the end points and directions of the valid rays; count [1] <- M.
+int psdf_trace_frame_select(int nr_rays, int nr_voxels_per_dim, float extent, const float* grid_translation,
+                            const uint8_t* grid_occupancy, float sphere_radius, const float* sphere_center, const float* points,
+                            const float* dirs, const uint8_t* no_hit, int* scratch, int* slot, float* pos, float* dirs_out,
+                            int* count, void* stream) {
+  if (nr_rays == 0) return PSDF_OK;
+  if (nr_rays < 0 || nr_voxels_per_dim < 1 || !grid_translation || !grid_occupancy || !sphere_center || !points || !dirs ||
+      !no_hit || !scratch || !slot || !pos || !dirs_out || !count)
+    return PSDF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int blocks = (int)psdf_blocks(nr_rays, PSDF_BLOCK);
+  int* block_counts = scratch;
+  int* block_offsets = scratch + blocks;
+  hipLaunchKernelGGL(trace_select_count_kernel, GRID1(nr_rays), nr_rays, mk_grid(nr_voxels_per_dim, extent, grid_translation),
+                     grid_occupancy, sphere_radius, sphere_center[0], sphere_center[1], sphere_center[2], points, no_hit, slot,
+                     block_counts);
+  hipLaunchKernelGGL(scan_i32_kernel, dim3(1), dim3(1024), 0, st, blocks, block_counts, block_offsets, count);
+  hipLaunchKernelGGL(trace_select_scatter_kernel, GRID1(nr_rays), nr_rays, block_offsets, points, dirs, slot, pos, dirs_out);
   PSDF_LAUNCH_CHECK();
   return PSDF_OK;
 }

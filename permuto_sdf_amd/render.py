@@ -1,5 +1,5 @@
-"""Frame renderer: a held-out view rendered volumetrically on the device into planar images (csrc/frame_rays.hip,
-csrc/frame_composite.hip, csrc/frame_plan.h).
+"""Frame renderer: a held-out view rendered on the device into planar images, volumetrically (csrc/frame_rays.hip,
+csrc/frame_composite.hip, csrc/frame_plan.h) or sphere-traced (csrc/sampling.hip: trace_select_*, csrc/frame_trace.hip).
 
 The reference renders its evaluation views with permuto_sdf_py/experiments/evaluation/create_my_images.py: run_net_in_chunks
 (train_permuto_sdf.py:172-209) over create_rays_from_frame (nerf_utils.py:459-500), 3 000 rays per chunk, every chunk's
@@ -9,7 +9,10 @@ results appended to Python lists, concatenated, and transposed into images (lin2
   * `frame_rays(frame, first, count)`         the rays of a range of pixels, bit-for-bit the rays training draws for them;
   * `FrameRenderer(trainer).render(frame)`    -> `RenderedFrame`: rgb, rgb_bg, normals, normals_cam, weights_sum as [C, H, W]
                                               float32 tensors on the device;
-  * `FrameRenderer.render_views(frames)`      -> [N, 3, H, W], what `image_eval.evaluate_views` takes.
+  * `FrameRenderer(trainer).render_traced(frame)` -> `TracedFrame`: rgb, normals, normals_cam, weights_sum, depth of the
+                                              surface a sphere trace finds (below);
+  * `FrameRenderer.render_views(frames)`      -> [N, 3, H, W], what `image_eval.evaluate_views` takes (`mode="traced"`: the
+                                              sphere-traced colours).
 
 A frame is cut into chunks by `psdf_frame_plan`: the largest multiple of 64 rays whose uniform samples cannot overflow the
 march's sample pool (32 768 rays at the reference's pool and 64 samples per ray: 59 chunks for 1600 x 1200 instead of 640).
@@ -18,9 +21,17 @@ the march's counts) -> SDF net with its input gradient (first order only) -> col
 radiance, normals and the weight sum at the chunk's pixel offset of the planes -> background net and one more launch that adds
 the background.  Evaluation mode throughout (no jitter), no colour calibration (the reference passes None).
 
+A sphere-traced frame is the reference's run_net_sphere_traced (train_permuto_sdf.py:211-242 over sdf_utils.py:120-218, called
+by render_from_frame.py:335): the surface render used for inspection and figures.  Chunks come from the same plan with one
+sample per ray (1920 x 1080 is one chunk).  Per chunk: rays -> `SphereTracer.trace` (end points, no gradients) -> one select
+call that keeps the rays whose end point lies in an occupied voxel strictly inside the bounding sphere and compacts them in ray
+order (one host wait, for their number M) -> SDF net with its input gradient and colour net on the M points (neither runs with
+M = 0) -> one resolve launch that writes colour, normal, coverage and depth at the chunk's pixel offset, zeros where nothing is
+hit.  One sample of weight 1 per ray: the planes hold the networks' outputs bit for bit.
+
 Rendering reads a training run and leaves it as it was: parameters, gradients, iteration and ray counters, `rgb.last_inv_s`
-(the occupancy refresh reads it) and the device's random state are not written.  Sphere-traced frames and image files are not
-handled here.  CPU tensors raise PsdfError: there is no CPU path.
+(the occupancy refresh reads it) and the device's random state are not written.  Image files are not handled here.  CPU tensors
+raise PsdfError: there is no CPU path.
 """
 import dataclasses
 import functools
@@ -31,6 +42,7 @@ import torch
 from . import _lib as L
 from .bridge import OccupancyGrid, Sphere
 from .encoding import PermutoEncodingFunc
+from .sphere_trace import SphereTracer
 
 _PLAN_FIELDS = 3            # PSDF_FRAME_PLAN_FIELDS of include/psdf.h
 _IT_WINDOW_OPEN = 9999999   # create_my_images.py:81: far past the coarse-to-fine schedule, every lattice level fully open
@@ -122,6 +134,28 @@ def frame_composite_nerf_raw(rs, raw_density, rgb, transmittance, height, width,
            L.c_i(int(height)), L.c_i(int(width)), L.c_l(int(pixel_first)), L.ptr(rgb_img), L.ptr(rgb_bg_img), L.stream())
 
 
+def trace_frame_select_raw(grid, sphere, pts, dirs, no_hit, scratch, slot, pos, dirs_out, count):
+    """csrc/sampling.hip, trace_select_*: the rays whose end point `pts` is a valid surface point (not `no_hit`, in an occupied
+    voxel of `grid`, strictly inside `sphere`), compacted in ray order -> slot [R] int32 (dense row or -1), pos / dirs_out
+    [>= M, 3], count [1] int32 = M; scratch: 2 * ceil(R / 256) int32"""
+    L.require_cuda(pts, dirs, no_hit, scratch, slot, pos, dirs_out, count)
+    L.call("psdf_trace_frame_select", L.c_i(pts.shape[0]), *grid._grid_args(), L.ptr(grid._occ()), L.c_f(sphere.m_radius),
+           (L.c_f * 3)(*sphere.m_center), L.ptr(pts), L.ptr(dirs), L.ptr(no_hit), L.ptr(scratch), L.ptr(slot), L.ptr(pos),
+           L.ptr(dirs_out), L.ptr(count), L.stream())
+
+
+def trace_frame_resolve_raw(slot, nr_valid, origins, dirs, pos, gradients, rgb, height, width, pixel_first, rgb_img, normals_img,
+                            weights_sum_img, depth_img, normals_cam_img=None, rot_cam_world=None):
+    """csrc/frame_trace.hip: the chunk's rays written into the planes at pixel_first + ray: colour, normalised gradient, 1 and
+    the depth along the ray for the rays with a slot (rows of the dense pos / gradients / rgb [nr_valid, 3], None with
+    nr_valid = 0), zeros for the others"""
+    L.require_cuda(slot, origins, dirs, rgb_img, normals_img, weights_sum_img, depth_img)
+    L.call("psdf_trace_frame_resolve", L.c_i(slot.shape[0]), L.c_i(int(nr_valid)), L.ptr(slot), L.ptr(origins), L.ptr(dirs),
+           L.ptr(pos), L.ptr(gradients), L.ptr(rgb), L.ptr(rot_cam_world), L.c_i(int(height)), L.c_i(int(width)),
+           L.c_l(int(pixel_first)), L.ptr(rgb_img), L.ptr(normals_img), L.ptr(normals_cam_img), L.ptr(weights_sum_img),
+           L.ptr(depth_img), L.stream())
+
+
 @dataclasses.dataclass
 class RenderedFrame:
     """float32 planes on the device: what run_net_in_chunks returns (train_permuto_sdf.py:204-209), plus the camera-frame
@@ -131,6 +165,17 @@ class RenderedFrame:
     normals: torch.Tensor                   # [3, H, W] normalised integral of the SDF gradient, world frame
     normals_cam: Optional[torch.Tensor]     # [3, H, W] the same in the camera's frame; None unless asked for
     weights_sum: torch.Tensor               # [1, H, W]
+
+
+@dataclasses.dataclass
+class TracedFrame:
+    """float32 planes on the device: what run_net_sphere_traced returns (train_permuto_sdf.py:237-242) as images, plus the
+    camera-frame normals when asked for and the depth"""
+    rgb: torch.Tensor                       # [3, H, W] the colour net at the surface point, 0 where nothing is hit (no background)
+    normals: torch.Tensor                   # [3, H, W] normalised SDF gradient at the surface point, world frame, 0 elsewhere
+    normals_cam: Optional[torch.Tensor]     # [3, H, W] the same in the camera's frame; None unless asked for
+    weights_sum: torch.Tensor               # [1, H, W] 1 where the ray ends on a valid surface point, else 0
+    depth: torch.Tensor                     # [1, H, W] dot(p - o, d): distance from the camera centre along the unit ray, else 0
 
 
 @functools.lru_cache(maxsize=None)
@@ -227,11 +272,7 @@ class FrameRenderer:
         march, which bounds the rays of a chunk (FramePlan)."""
         t = self.trainer
         hp = t.hp
-        L.require_cuda(frame.K, frame.tf_world_cam)
-        dev = frame.K.device
-        models_dev = t.sdf.encoding.lattice_values.device       # (a tensor's device carries its index; `t.dev` may be a bare "cuda")
-        if dev != models_dev or frame.tf_world_cam.device != dev:      # the kernels take raw pointers: no one else would notice
-            raise L.PsdfError("the frame lives on %s, the models on %s" % (dev, models_dev))
+        dev = self._check_devices(frame)
         H, W = frame.height, frame.width
         plan = FramePlan(H, W, hp.max_nr_samples_per_ray, pool_samples)
         it = _IT_WINDOW_OPEN if it is None else it
@@ -258,11 +299,78 @@ class FrameRenderer:
             t.grid.max_nr_samples = grid_pool
         return out
 
-    def render_views(self, frames, **kwargs):
-        """-> [N, 3, H, W] float32: the rgb of every frame (all of one size), ready for image_eval.evaluate_views"""
+    def _check_devices(self, frame):
+        """the kernels take raw pointers: no one else would notice a frame on another device than the models"""
+        L.require_cuda(frame.K, frame.tf_world_cam)
+        dev = frame.K.device
+        models_dev = self.trainer.sdf.encoding.lattice_values.device    # (a tensor's device carries its index; `t.dev` may be a bare "cuda")
+        if dev != models_dev or frame.tf_world_cam.device != dev:
+            raise L.PsdfError("the frame lives on %s, the models on %s" % (dev, models_dev))
+        return dev
+
+    def _traced_chunk(self, frame, first, count, tracer, trace_args, it, out, rot, work):
+        """one chunk of a sphere-traced frame, start to finish"""
+        t = self.trainer
+        scratch, slot, pos, dirs, nr_valid = work
+        o, d = frame_rays(frame, first, count)
+        pts = tracer.trace(o, d, *trace_args, return_gradients=False)[0]
+        trace_frame_select_raw(t.grid, t.sphere, pts, d, tracer.no_hit, scratch, slot[:count], pos, dirs, nr_valid)
+        # the one host wait of the chunk: how many rays ended on the surface
+        pinned = t._pinned(1)
+        pinned[:1].copy_(nr_valid, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        event.synchronize()
+        M = int(pinned[0])
+        if M == 0:
+            p = grad = rgb = None
+        else:
+            p = pos[:M]
+            _, grad, feat = self._sdf_and_gradient(p, it)
+            rgb = _f32(t.rgb(p, dirs[:M], grad, feat))
+            grad = _f32(grad)
+        trace_frame_resolve_raw(slot[:count], M, o, d, p, grad, rgb, frame.height, frame.width, first, out.rgb, out.normals,
+                                out.weights_sum, out.depth, out.normals_cam, rot)
+
+    @torch.no_grad()
+    def render_traced(self, frame, it=None, nr_sphere_traces=15, sdf_multiplier=0.9, sdf_converged_tresh=2e-4,
+                      camera_normals=False, max_rays_per_chunk=OccupancyGrid.POOL):
+        """-> TracedFrame: the surface a sphere trace finds, as run_net_sphere_traced renders it.  Defaults as
+        render_from_frame.py:335; `it` as in `render` (None: the lattice window fully open).  max_rays_per_chunk bounds the rays
+        traced at once (FramePlan with one sample per ray)."""
+        t = self.trainer
+        dev = self._check_devices(frame)
+        H, W = frame.height, frame.width
+        plan = FramePlan(H, W, 1, max_rays_per_chunk)
+        it = _IT_WINDOW_OPEN if it is None else it
+        t._params_ready()                     # a data-parallel trainer's parameters may still be on their way
+        net = t.sdf
+        tracer = SphereTracer(net.encoding, net.mlp_sdf, t.grid, t.sphere, _f32(net.window(it)))
+
+        def planes(c):
+            return torch.empty((c, H, W), dtype=torch.float32, device=dev)      # every pixel belongs to one chunk, which writes it
+
+        out = TracedFrame(rgb=planes(3), normals=planes(3), normals_cam=planes(3) if camera_normals else None,
+                          weights_sum=planes(1), depth=planes(1))
+        rot = frame.rot_cam_world() if camera_normals else None
+        R = plan.rays_per_chunk
+        work = (torch.empty(2 * ((R + 255) // 256), dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.int32, device=dev),
+                torch.empty((R, 3), dtype=torch.float32, device=dev), torch.empty((R, 3), dtype=torch.float32, device=dev),
+                torch.empty(1, dtype=torch.int32, device=dev))
+        for first, count in plan.chunks():
+            self._traced_chunk(frame, first, count, tracer, (nr_sphere_traces, sdf_multiplier, sdf_converged_tresh), it, out, rot,
+                               work)
+        return out
+
+    def render_views(self, frames, mode="volumetric", **kwargs):
+        """-> [N, 3, H, W] float32: the rgb of every frame (all of one size), ready for image_eval.evaluate_views; mode
+        "volumetric": `render`, "traced": `render_traced`"""
+        if mode not in ("volumetric", "traced"):
+            raise ValueError("mode must be 'volumetric' or 'traced', got %r" % (mode,))
+        render = self.render if mode == "volumetric" else self.render_traced
         frames = list(frames)
         if not frames:
             raise ValueError("render_views needs at least one frame")
         if len({(f.height, f.width) for f in frames}) != 1:
             raise ValueError("render_views takes frames of one size")
-        return torch.stack([self.render(f, **kwargs).rgb for f in frames])
+        return torch.stack([render(f, **kwargs).rgb for f in frames])
