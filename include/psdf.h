@@ -657,6 +657,74 @@ int psdf_mesh_nn_cooperative(const float* queries, int64_t nq, const int32_t* qu
 int psdf_mesh_nn_ring(const float* queries, int64_t nq, const float* refs, int64_t nr, const int32_t* cell_start, const float*
     origin_edge, const int* dims, float max_dist, float* dist, int32_t* idx, const uint8_t* open, void* stream);
 
+/* ---- mesh_clean.hip ---- */
+/* What the reference does to an extracted mesh before it scores it, on device tensors: the box cull of
+   permuto_sdf_py/experiments/evaluation/create_my_meshes.py:72-75 and, for scenes trained without masks, the mask cull, face
+   filter and largest component of permuto_sdf_py/experiments/evaluation/evaluate_chamfer_distance.py:110-167.  The entries
+   allocate nothing and never synchronise; sorts and scans are the caller's; an empty batch returns 0 before any pointer check.
+   Two rules are restated from their libraries' published behaviour and are UNPINNED here (neither library is available to the
+   tests): the row spans of OpenCV's MORPH_ELLIPSE (the caller passes them in) and trimesh's face adjacency (an edge links two
+   faces iff it occurs in exactly two half-edges).  *flag (int32, zeroed by the caller): |= 2 a face names a vertex outside
+   [0, nV); |= 4 a union-find loop exceeded its cap (psdf_mesh_clean_union_find_cap). */
+/* host only: the launch plan of the dilation (csrc/mesh_clean_plan.h) for n views of H x W and an element whose row k has the
+   half-width half_widths[k] (count rows, odd) -> out [PSDF_MESH_CLEAN_PLAN_FIELDS] int64: 0 the radius r = count / 2; 1 output
+   rows per workgroup; 2 rows staged in LDS (field 1 + 2 r); 3, 4 tiles along x and y; 5 packed words per row, ceil(W / 32); 6
+   workgroups of psdf_mesh_clean_dilate; 7 workgroups of psdf_mesh_clean_row_distance; 8 bytes of LDS of a dilation workgroup.
+   -1: n < 0, H or W < 1, an even or empty element, a half-width outside [0, 254]; -2: more than 255 rows, or more than 2^31 - 1
+   workgroups */
+#define PSDF_MESH_CLEAN_PLAN_FIELDS 9
+int psdf_mesh_clean_dilate_plan(int64_t n, int64_t H, int64_t W, const int* half_widths, int64_t count, int64_t* out);
+/* host only: the iteration cap of the union-find loops over n nodes, n + 1 */
+int64_t psdf_mesh_clean_union_find_cap(int64_t n);
+/* replaces: the threshold `> 128` of evaluate_chamfer_distance.py:135 (moved before the dilation: dilating and thresholding
+   commute for a flat element) and the horizontal half of cv.dilate (:134).  masks [n, H, W] uint8; hd [n, H, W] uint8 <-
+   distance along the row to the nearest pixel with value > threshold, 255 when that is 255 or more or the row has none */
+int psdf_mesh_clean_row_distance(const uint8_t* masks, int64_t n, int H, int W, int threshold, uint8_t* hd, void* stream);
+/* replaces: cv.getStructuringElement(cv.MORPH_ELLIPSE, (101, 101)) and cv.dilate, evaluate_chamfer_distance.py:133-134, for any
+   element made of centred row spans.  half_widths [count]: a HOST array; words [n, H, ceil(W / 32)] int32 <- the dilated masks,
+   pixel (y, x) at bit x & 31 of word x >> 5, padding bits 0: set iff hd[y + dy, x] <= half_widths[dy + r] for a dy with y + dy
+   inside the image (nothing is set outside it: cv.dilate's default border) */
+int psdf_mesh_clean_dilate(const uint8_t* hd, int64_t n, int H, int W, const int* half_widths, int count, int32_t* words, void*
+    stream);
+/* replaces: clean_points_by_mask, evaluate_chamfer_distance.py:110-143 (the projection of :130-132, the ones-padded image and the
+   clipped lookup of :137-140, the AND of :142).  V [nV, 3] fp32; world_mats [views, 12] float64: the first three rows of every
+   world_mat_i; keep [nV] bytes <- 1 iff every view keeps the vertex: p = ((P0 x + P1 y) + P2 z) + P3 per row in float64, u = p0 /
+   p2, v = p1 / p2 rounded half to even; with 0 <= u < W and 0 <= v < H the view keeps it iff bit (v, u) of its words is set,
+   otherwise -- and for a non-finite u or v -- it keeps it.  No test of the sign of p2: the reference has none. */
+int psdf_mesh_clean_inside_masks(const float* V, int64_t nV, const double* world_mats, int views, const int32_t* words, int H, int
+    W, uint8_t* keep, void* stream);
+/* replaces: faces_mask of evaluate_chamfer_distance.py:151.  face_keep [nF] bytes <- 1 iff keep [nV] is set for the face's three
+   vertices (and face_mask [nF], optional, for the face); a face out of range raises the flag and is dropped */
+int psdf_mesh_clean_face_keep(const int32_t* F, int64_t nF, const uint8_t* keep, int64_t nV, const uint8_t* face_mask, uint8_t*
+    face_keep, int32_t* flag, void* stream);
+/* replaces: indexes and new_vertices of evaluate_chamfer_distance.py:147-149 and :156 (remove_marked_vertices(mask, True) for
+   the box cull).  incl [nV] int32: the caller's INCLUSIVE scan of keep; a kept vertex moves to row incl - 1 of V_out (NV_out
+   [.., 3] fp32 and edges_out [.., 2] int64 where NV / edges are given); vertex_map [nV] int32 <- the new row, -1 where removed */
+int psdf_mesh_clean_emit_vertices(int64_t nV, const uint8_t* keep, const int32_t* incl, const float* V, const float* NV, const
+    int64_t* edges, float* V_out, float* NV_out, int64_t* edges_out, int32_t* vertex_map, void* stream);
+/* replaces: new_faces of evaluate_chamfer_distance.py:152-155.  incl [nF] int32: the caller's inclusive scan of face_keep; a kept
+   face moves to row incl - 1 of F_out, renumbered through vertex_map */
+int psdf_mesh_clean_emit_faces(const int32_t* F, int64_t nF, const uint8_t* face_keep, const int32_t* incl, const int32_t*
+    vertex_map, int32_t* F_out, void* stream);
+/* replaces: the edge matching inside trimesh's Trimesh.split(only_watertight=False), evaluate_chamfer_distance.py:160
+   (face_adjacency: rows of the sorted edges that occur exactly twice).  keys [3 nF] int64 <- (min << 32) | max of the half-edge
+   e of face f at slot 3 f + e */
+int psdf_mesh_clean_edge_keys(const int32_t* F, int64_t nF, int64_t nV, int64_t* keys, int32_t* flag, void* stream);
+/* sorted_keys [3 nF] ascending and slot [3 nF] int64, the slot each key came from (the caller's stable sort): unites the two
+   faces slot / 3 of every run of exactly two equal keys whose endpoints differ.  parent [nF] int32: the caller's 0 .. nF - 1;
+   the larger root is hooked under the smaller by compare-and-swap, so parent[i] <= i throughout */
+int psdf_mesh_clean_link_edges(const int64_t* sorted_keys, const int64_t* slot, int64_t nF, int32_t* parent, int32_t* flag, void*
+    stream);
+/* vertex connectivity: unites the three vertices of every face in parent [nV] (the caller's 0 .. nV - 1) */
+int psdf_mesh_clean_link_vertices(const int32_t* F, int64_t nF, int64_t nV, int32_t* parent, int32_t* flag, void* stream);
+/* replaces: the connected-components labelling of Trimesh.split.  labels [n] int32 <- the root of every node, the smallest index
+   of its component; sizes [n] int32 (optional, zeroed by the caller) += 1 at every node's label */
+int psdf_mesh_clean_flatten(int32_t* parent, int64_t n, int32_t* labels, int32_t* sizes, int32_t* flag, void* stream);
+/* vertex connectivity: vertex_label [nV] from psdf_mesh_clean_flatten; first_face [nV] int32 (filled with INT32_MAX by the
+   caller) <- the smallest face of every vertex component; labels [nF] <- that face for every face; sizes [nF] (zeroed) += 1 */
+int psdf_mesh_clean_face_labels(const int32_t* F, int64_t nF, int64_t nV, const int32_t* vertex_label, int32_t* first_face,
+    int32_t* labels, int32_t* sizes, void* stream);
+
 /* ---- image_eval.hip ---- */
 /* The image scores of the reference's held-out views (permuto_sdf_py/experiments/evaluation/evaluate_psnr.py: piq.psnr and
    piq.ssim on both images times the mask) on device tensors, accumulated in float64 without floating-point atomics: the same
