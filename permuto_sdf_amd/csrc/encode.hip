@@ -986,6 +986,46 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   grad_positions[e] = grad_positions[e] + s;
 }
 
+// Four consecutive entries of one queue: what a thread of the reduce kernel loads per step.  Rows stay packed as they lie in
+// the queue (two 16-bit rows per register) until they are added.
+template <int F>
+struct QueueGroup {
+  uint32_t r01, r23;
+  float v[4 * F];   // entry k, feature f at [k * F + f]: the order in memory
+};
+
+// One 8-byte load of the rows and F 16-byte loads of the values.  i0: the group's first entry, a multiple of 4 counted from
+// the start of the workspace arrays.  Unconditional, so that the compiler can count the loads in flight (a load under a
+// divergent branch makes it wait for ALL outstanding loads before the first use, the prefetched ones included).
+template <int F>
+__device__ __forceinline__ void queue_group_load(const uint16_t* __restrict__ rows, const float* __restrict__ vals, int i0,
+                                                 QueueGroup<F>& G) {
+  const uint2 r = *reinterpret_cast<const uint2*>(rows + i0);
+  G.r01 = r.x;
+  G.r23 = r.y;
+  const float4* __restrict__ p = reinterpret_cast<const float4*>(vals + (int64_t)i0 * F);
+#pragma unroll
+  for (int k = 0; k < F; k++) {
+    const float4 t = p[k];
+    G.v[4 * k] = t.x;
+    G.v[4 * k + 1] = t.y;
+    G.v[4 * k + 2] = t.z;
+    G.v[4 * k + 3] = t.w;
+  }
+}
+
+// Adds a group to the LDS slice, entry after entry.  (All four reads, then all four compare-and-swaps, with same-row entries
+// merged in registers first, was built and measured: no faster, 55 instead of 44 registers -- profiles/enc_bwd_reduce_ab.txt.)
+template <int F>
+__device__ __forceinline__ void queue_group_fold(float* tab, const QueueGroup<F>& G, int& hot) {
+  const uint32_t r[4] = {G.r01 & 0xFFFFu, G.r01 >> 16, G.r23 & 0xFFFFu, G.r23 >> 16};
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+#pragma unroll
+    for (int f = 0; f < F; f += 2) lds_add_pair(&tab[r[k] * F + f], G.v[k * F + f], G.v[k * F + f + 1], hot);
+  }
+}
+
 // One workgroup per (partition, level): fold the queue into an LDS image of the partition's table slice (64-bit
 // compare-and-swap per feature pair, lds_add_pair), then add the slice to the gradient table (plain read-modify-write:
 // this workgroup is the only writer of these rows after the binning kernel has finished).
@@ -1003,44 +1043,65 @@ __global__ void __launch_bounds__(1024)
   const int64_t qb = ((int64_t)level * Q.np + part) * Q.cap;
   const uint16_t* __restrict__ rows = Q.rows + qb;
   const float* __restrict__ vals = Q.vals + qb * F;
-#if !defined(PSDF_ENC_REDUCE_U)
-#define PSDF_ENC_REDUCE_U 8
-#endif
-  // queue entries in flight per thread (the loop is HBM-latency bound otherwise); measured on the bench step, encode backward
-  // pair: U = 4 0.847 ms, 8 0.742, 12 0.742, 16 0.750
-  constexpr int U = PSDF_ENC_REDUCE_U;
+  const int tid = threadIdx.x, nt = blockDim.x;
   int hot = 0;
-  for (int base = 0; base < n; base += U * (int)blockDim.x) {
-    int row[U];
-    float v[U][F];
+  // A thread takes four consecutive entries per step, in groups that are 4-entry aligned in the WORKSPACE (queue_plan aligns
+  // the arrays to 256 bytes, but a queue's capacity need not be a multiple of 4, so its first entry need not be aligned):
+  // entries [0, head) and [head + 4 nfull, n) are the ragged ends, at most three each, and take the scalar form.
+  const bool wide = ((reinterpret_cast<uintptr_t>(Q.rows) & 7) | (reinterpret_cast<uintptr_t>(Q.vals) & 15)) == 0;
+  const int lead = (int)((4 - (qb & 3)) & 3);
+  const int head = wide ? (lead < n ? lead : n) : n;   // (a workspace that is not 16-byte aligned: everything in the scalar form)
+  const int nfull = (n - head) >> 2;
+  const int tail0 = head + 4 * nfull;
+  for (int i = tid; i < head + (n - tail0); i += nt) {
+    const int e = i < head ? i : tail0 + (i - head);
 #pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int i = base + u * (int)blockDim.x + (int)threadIdx.x;
-      row[u] = (i < n) ? (int)rows[i] : -1;
-      if (F == 2) {
-        const float2 t = (i < n) ? *reinterpret_cast<const float2*>(vals + (int64_t)i * 2) : make_float2(0.f, 0.f);
-        v[u][0] = t.x;
-        v[u][F - 1] = t.y;
-      } else {
-#pragma unroll
-        for (int f = 0; f < F; f++) v[u][f] = (i < n) ? vals[(int64_t)i * F + f] : 0.f;
-      }
+    for (int f = 0; f < F; f += 2) lds_add_pair(&tab[(int)rows[e] * F + f], vals[(int64_t)e * F + f], vals[(int64_t)e * F + f + 1], hot);
+  }
+  if (nfull > 0) {
+    // Two groups per thread alternate: the loads of one are issued before the adds of the other.  A thread past the last
+    // group loads the last group again and does not add it.
+    // Every workgroup starts its walk at another place of its queue (and wraps round): the queues lie a fixed stride apart, and
+    // workgroups that all read the same offset of their queues at the same time measured 4 % slower (the order of the
+    // additions was never fixed: it depends on which compare-and-swap lands first).
+    const int last = nfull - 1;
+    const int rot = (int)((((uint32_t)(level * Q.np + part) * 2654435761u) >> 8) % (uint32_t)nfull);
+    const auto at = [&](int g) {   // first entry of the g-th group of the walk
+      int m = (g < last ? g : last) + rot;
+      if (m >= nfull) m -= nfull;
+      return head + 4 * m;
+    };
+    QueueGroup<F> A, B;
+    queue_group_load<F>(rows, vals, at(tid), A);
+    for (int base = 0; base < nfull; base += 2 * nt) {
+      const int g = base + tid;
+      queue_group_load<F>(rows, vals, at(g + nt), B);
+      if (g < nfull) queue_group_fold<F>(tab, A, hot);
+      queue_group_load<F>(rows, vals, at(g + 2 * nt), A);
+      if (g + nt < nfull) queue_group_fold<F>(tab, B, hot);
     }
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      if (row[u] >= 0) {
-#pragma unroll
-        for (int f = 0; f < F; f += 2) lds_add_pair(&tab[row[u] * F + f], v[u][f], v[u][f + 1], hot);
-      }
   }
   __syncthreads();
   const int64_t row0 = (int64_t)part << Q.shift;
   int64_t nrows = (int64_t)capacity - row0;
   if (nrows > rpp) nrows = rpp;
   float* __restrict__ out = grad_lattice + ((int64_t)level * capacity + row0) * F;
-  for (int64_t i = threadIdx.x; i < nrows * F; i += blockDim.x) {
-    const float v = tab[i];
-    if (v != 0.f) out[i] = out[i] + v;
+  // Eight floats per thread and step, their loads issued together (one at a time, the 16 steps of a 64-KiB slice were 16
+  // dependent trips to memory at the end of every workgroup).  The loads are unconditional for the same reason as in
+  // queue_group_load -- a step past the end reads the slice's last float -- and only sums that changed are stored.
+  const int lim = (int)(nrows * F);
+  constexpr int EU = 8;
+  for (int i0 = tid; i0 < lim; i0 += EU * nt) {
+    float t[EU], o[EU];
+#pragma unroll
+    for (int j = 0; j < EU; j++) {
+      const int i = i0 + j * nt;
+      t[j] = i < lim ? tab[i] : 0.f;
+      o[j] = out[i < lim ? i : lim - 1];
+    }
+#pragma unroll
+    for (int j = 0; j < EU; j++)
+      if (t[j] != 0.f) out[i0 + j * nt] = o[j] + t[j];
   }
 }
 
