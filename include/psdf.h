@@ -762,6 +762,43 @@ int psdf_image_ssim(const void* pred, int pred_u8, const int64_t* pred_strides, 
     int kernel_size, double kernel_sigma, double k1, double k2, int downsample, double* workspace, double* out, double* map,
     void* stream);
 
+/* ---- sdf_fit.hip ---- */
+/* Fitting the SDF network to an oriented point cloud (permuto_sdf_py/train_sdf_from_mesh.py, train_4d_sdf.py): the batch of a
+   step and the loss tail.  P is the dimension of a position: 3, or 4 with time as the last column.  n_surf rows on the surface
+   come first, n_off rows off it follow; N = n_surf + n_off.  The entries allocate nothing and never synchronise; N = 0 returns 0
+   before any pointer is looked at; -1 for a negative count, another P, a NULL pointer that is needed; -2 for a count beyond
+   2^31 - 1. */
+/* host only: the launch plan (csrc/sdf_fit_plan.h) -> out [PSDF_SDF_FIT_PLAN_FIELDS] int64: 0 workgroups of the loss kernel
+   (= partial sums per term), 1 bytes of psdf_sdf_fit_loss's workspace, 2 rows one pass of the full loss grid covers, 3
+   workgroups of the batch kernel */
+#define PSDF_SDF_FIT_PLAN_FIELDS 4
+int psdf_sdf_fit_plan(int64_t n_surf, int64_t n_off, int64_t* out);
+/* replaces: the batch of train_sdf_from_mesh.py:118-123 and train_4d_sdf.py:200-208 (randint, index_select of points and
+   normals, rand_points_inside, rand, two cat), the random numbers coming from the caller (torch's generator).  points [N, P]:
+   rows r < n_surf <- cloud_points [M, P] row indices[r], the others <- lo[c] + uniforms[r - n_surf, c] * (hi[c] - lo[c]), one
+   rounding per operation; normals [n_surf, 3] <- cloud_normals [M, 3] row indices[r].  lo, hi: HOST arrays of P floats.
+   indices: int64 on the device.  AN INDEX IS CLAMPED TO [0, M - 1]: no index can make the kernel read outside the cloud.
+   -1 also for M < 1 with n_surf > 0 */
+int psdf_sdf_fit_batch(int P, int64_t M, int64_t n_surf, int64_t n_off, const float* cloud_points, const float* cloud_normals,
+    const int64_t* indices, const float* uniforms, const float* lo, const float* hi, float* points, float* normals, void*
+    stream);
+/* replaces: sdf_loss, permuto_sdf_py/utils/sdf_utils.py:16-57, the division by 30000 behind it (train_sdf_from_mesh.py:136) and
+   torch autograd of both.  sdf [N], gradients [N, P] (g: the first three columns, train_4d_sdf.py:213), normals [n_surf, 3];
+   weights: HOST array of 4 floats (the reference's 5e1, 1e2, 3e3, 1e2).  terms [4] (device) <- the unweighted means
+     0 over N:       w | |g| - 1 |, w = exp(-s^2 / (2 eik_clamp^2)) for eik_clamp > 0, else 1; w is not differentiated
+     1 over n_surf:  1 - g . n / (max(|g|, 1e-8) max(|n|, 1e-8))      (F.cosine_similarity)
+     2 over n_surf:  |s|
+     3 over n_off:   exp(-sharpness |s|)
+   with sign(0) = 0, the gradient of |g| at 0 equal to 0, the clamps of term 1 acting on the norms' values only (their
+   derivatives stay those of the norms, as in torch), and 0 for a mean over no rows.  loss [1] (optional) <- loss +
+   scale * sum_k weights[k] terms[k].  grad_sdf [N], grad_gradients [N, P] (both or none) <- the gradient of that sum; the time
+   column of grad_gradients is written as 0.  workspace: out[1] bytes of psdf_sdf_fit_plan.  No floating-point atomics: partial
+   sums per workgroup of a fixed grid, added in double in a fixed order by a finishing launch -- the same inputs give the same
+   bits on every call.  -1 also for a NaN weight, sharpness, eik_clamp or scale */
+int psdf_sdf_fit_loss(int P, int64_t n_surf, int64_t n_off, const float* sdf, const float* gradients, const float* normals,
+    const float* weights, float sharpness, float eik_clamp, float scale, double* workspace, float* terms, float* loss, float*
+    grad_sdf, float* grad_gradients, void* stream);
+
 /* ---- frame_trace.hip ---- */
 /* replaces: what run_net_sphere_traced does after the networks (permuto_sdf_py/train_permuto_sdf.py:224-242: the integrals of
    colour and SDF gradient with one sample per ray and a weight in {0, 1}, F.normalize, the weight sum, lin2nchw) and

@@ -6,7 +6,8 @@ HIP kernels through the C-ABI library declared in include/psdf.h.  No CPU fallba
 from . import _lib
 from . import image_eval
 from . import render
+from . import sdf_fit
 from .encoding import PermutoEncoding, Coarse2Fine
 from .mlp import FusedMLP, LipshitzMLP
 
-__all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval", "render"]
+__all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval", "render", "sdf_fit"]

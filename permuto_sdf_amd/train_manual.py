@@ -96,6 +96,32 @@ def _net(mlp):
     return mlp.dims, layers, [l.weight for l in layers], [l.bias for l in layers]
 
 
+def sdf_gradient(enc, feat, pts, net, zeroed=None):
+    """n = d sdf / d p and the feature gradient it came through, for the SDF network (encoding `enc`, MLP `net`: a record with
+    dims, ws, bs, win) evaluated at pts with features feat -> (n [N, P], dfeat [C, N], e0).  zeroed: a zero-filled [N, P] tensor
+    for n (one is filled here otherwise)"""
+    e0 = None       # "the unit gradient of output 0": the kernels take NULL for it (no [33, N] tensor that is 1 in one row)
+    dfeat, _, _ = mlp_backward_raw(net.dims, feat, net.ws, net.bs, e0, need_dx=True, need_dw=False)
+    n = _enc_bwd(enc, pts, net.win, dfeat, want_pos=True, want_lattice=False, zeroed=zeroed)
+    return n, dfeat, e0
+
+
+def sdf_gradient_backward(enc, mlp_module, g_n, feat, dfeat, e0, pts, net, extra_dfeat=None, extra_gy=None, zeroed=None):
+    """backward of  n = d sdf / d p  for an upstream g_n [N, P]: lattice and parameter gradients are accumulated (into the
+    encoding's touched-rows buffer and net.gb); returns the position gradient when `zeroed`, a zero-filled [N, P] tensor for it,
+    is given (the shifted points of the curvature term depend on n).  extra_gy [33, N]: an upstream gradient of the net's outputs
+    on the same samples -- its plain backward rides in the double backward's launch (round 6: one forward recomputation and one
+    sweep for both); extra_dfeat: a data gradient to add instead (the two-launch form)"""
+    win = net.win
+    gg = _enc_dbl_gather(enc, pts, win, g_n, dfeat)
+    dX2, _, _ = mlp_double_backward(net.dims, feat, net.ws, net.bs, e0, gg, into=(net.gb.dWs, net.gb.dbs), module=mlp_module,
+                                    gy2_fm=extra_gy)
+    if extra_dfeat is not None:
+        dX2 = dX2 + extra_dfeat
+    _enc_dbl_scatter(enc, pts, win, g_n, dfeat, dX2)
+    return _enc_bwd(enc, pts, win, dX2, want_pos=True, want_lattice=False, zeroed=zeroed) if zeroed is not None else None
+
+
 class _Step:
     """What `_main_forward` hands to `_main_backward`: every field exists from the start, None until its stage has run, so the
     backward tests the field (calib, g_cw_bg, g_cb_bg: colour calibration; fg, g_n: foreground samples; curv: curvature weight
@@ -213,11 +239,7 @@ class ManualTrainer(Trainer):
 
     # ------------------------------------------------------------------ the SDF network, one evaluation
     def _sdf_gradient(self, feat, pts, net):
-        """n = d sdf / d p and the feature gradient it came through"""
-        e0 = None       # "the unit gradient of output 0": the kernels take NULL for it (no [33, N] tensor that is 1 in one row)
-        dfeat, _, _ = mlp_backward_raw(net.dims, feat, net.ws, net.bs, e0, need_dx=True, need_dw=False)
-        n = _enc_bwd(self.sdf.encoding, pts, net.win, dfeat, want_pos=True, want_lattice=False, zeroed=self._zeroed_pos(pts))
-        return n, dfeat, e0
+        return sdf_gradient(self.sdf.encoding, feat, pts, net, self._zeroed_pos(pts))
 
     def _zeroed_pos(self, pts):
         """a zero-filled [N, 3] tensor for a position gradient: the step needs three of the same size (normals of the samples, of
@@ -247,18 +269,8 @@ class ManualTrainer(Trainer):
         return views[0], views[1], views[2], flat[offs[3]:offs[4]]
 
     def _sdf_gradient_backward(self, g_n, feat, dfeat, e0, pts, net, want_pos=False, extra_dfeat=None, extra_gy=None):
-        """backward of  n = d sdf / d p  for an upstream g_n [N,3]: lattice and parameter gradients are accumulated; returns the
-        position gradient when asked (the shifted points of the curvature term depend on n).  extra_gy [33, N]: an upstream
-        gradient of the net's outputs on the same samples -- its plain backward rides in the double backward's launch (round 6:
-        one forward recomputation and one sweep for both); extra_dfeat: a data gradient to add instead (the two-launch form)"""
-        enc, win = self.sdf.encoding, net.win
-        gg = _enc_dbl_gather(enc, pts, win, g_n, dfeat)
-        dX2, _, _ = mlp_double_backward(net.dims, feat, net.ws, net.bs, e0, gg, into=(net.gb.dWs, net.gb.dbs), module=self.sdf.mlp_sdf,
-                                        gy2_fm=extra_gy)
-        if extra_dfeat is not None:
-            dX2 = dX2 + extra_dfeat
-        _enc_dbl_scatter(enc, pts, win, g_n, dfeat, dX2)
-        return _enc_bwd(enc, pts, win, dX2, want_pos=True, want_lattice=False, zeroed=self._zeroed_pos(pts)) if want_pos else None
+        return sdf_gradient_backward(self.sdf.encoding, self.sdf.mlp_sdf, g_n, feat, dfeat, e0, pts, net, extra_dfeat=extra_dfeat,
+                                     extra_gy=extra_gy, zeroed=self._zeroed_pos(pts) if want_pos else None)
 
     # ------------------------------------------------------------------ the background branch (NerfHash, models.py:431-526)
     def _bg_forward(self, bg, calib):
