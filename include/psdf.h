@@ -762,6 +762,53 @@ int psdf_image_ssim(const void* pred, int pred_u8, const int64_t* pred_strides, 
     int kernel_size, double kernel_sigma, double k1, double k2, int downsample, double* workspace, double* out, double* map,
     void* stream);
 
+/* ---- nerf_render.hip ---- */
+/* NeRF training of a foreground (permuto_sdf_py/train_nerf.py): the rendering of a packed container with all three per-ray
+   outputs and their gradients, the loss tail, and the glue between NerfHash's two nets.  The entries allocate nothing and never
+   synchronise; a count <= 0 returns 0 before any pointer is looked at. */
+/* host only: the launch plan (csrc/nerf_render_plan.h) -> out [PSDF_NERF_RENDER_PLAN_FIELDS] int64: 0 workgroups of the loss
+   kernel (= partial sums per term), 1 bytes of psdf_nerf_loss's workspace, 2 rays one pass of the full loss grid covers, 3 the
+   register chunks K of 64 samples psdf_nerf_render_backward holds for max_per_ray (1, 2 or 4).
+   -1: nr_rays < 0, max_per_ray < 1, out NULL; -2: nr_rays > (2^31 - 1) / 3, max_per_ray > 256 */
+#define PSDF_NERF_RENDER_PLAN_FIELDS 4
+int psdf_nerf_render_plan(int64_t nr_rays, int max_per_ray, int64_t* out);
+/* replaces: NerfHash's softplus (models.py:517), VolumeRenderingNerf.compute_weights + integrate (volume_rendering_modules.py:
+   72-86,176-190) as train_nerf.py:70-71 calls them for the FOREGROUND.  Ray-index arguments, raw_density [M], dt [M], rgb [M,3]
+   as psdf_nerf_composite_forward.  pred [R,3] <- sum w rgb (the sweep and the summation order of psdf_nerf_composite_forward:
+   the same bits as its pred_bg), weights_sum [R] <- sum w, bg_transmittance [R] <- T of the ray's last sample; each output may
+   be NULL on its own (rgb may be NULL when pred is).  Empty and overflowed rays: 0, 0 and 1.  Any ray length.
+   -1: every output NULL, or a NULL input that is needed */
+int psdf_nerf_render_forward(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, const float*
+    raw_density, const float* dt, const float* rgb, float* pred, float* weights_sum, float* bg_transmittance, void* stream);
+/* Backward of the above for upstream grad_pred [R,3], grad_weights_sum [R], grad_bg_transmittance [R]: each may be NULL (= no
+   gradient arrives there), at least one is given.  grad_raw_density [M]; grad_rgb [M,3] optional (zeros without grad_pred).
+   The weight gradient of a sample is <grad_pred, rgb> + grad_weights_sum; max_per_ray and reference_compat as in
+   psdf_nerf_composite_backward: a ray longer than declared gets NaN in every gradient, max_per_ray > 256 -> -2.  Samples of
+   rays the reference skips (empty, overflowed) are not written: zero-fill the outputs when the container can hold such rays. */
+int psdf_nerf_render_backward(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, int max_per_ray,
+    const float* grad_pred, const float* grad_weights_sum, const float* grad_bg_transmittance, const float* raw_density, const
+    float* dt, const float* rgb, int reference_compat, float* grad_raw_density, float* grad_rgb, void* stream);
+/* replaces: train_nerf.py:203-207 and torch autograd of it.  pred, gt [R,3]; hit: uint8 [R] or NULL (= 1).  terms [2] (device)
+   <- 0: mean over 3 R of (gt - pred)^2 hit[ray];  1: mean over R of BCE(clip(weights_sum, 1e-3, 1 - 1e-3), gt_mask), computed
+   when weights_sum and gt_mask [R] are given (both or neither), else 0.  loss [1] (optional) <- loss + terms[0] + mask_weight
+   terms[1] (the reference's mask_weight: 0.1).  grad_pred [R,3] (optional) and grad_weights_sum [R] (optional) <- the gradient
+   of that sum; grad_weights_sum is 0 where the clip is active (a value AT a bound passes, as in torch.clamp) and without the
+   mask term.  workspace: out[1] bytes of psdf_nerf_render_plan.  No floating-point atomics: partial sums per workgroup of a
+   fixed grid, added in double in a fixed order by a finishing launch -- the same inputs give the same bits on every call.
+   -1 also for a NaN mask_weight; -2 for nr_rays > (2^31 - 1) / 3 */
+int psdf_nerf_loss(int64_t nr_rays, const float* pred, const float* gt, const unsigned char* hit, const float* weights_sum,
+    const float* gt_mask, float mask_weight, double* workspace, float* terms, float* loss, float* grad_pred, float*
+    grad_weights_sum, void* stream);
+/* replaces: between NerfHash's two nets (models.py:509-513) gelu + t() + cat.  fd [65, M] the density net's feature-major
+   output (row 0: the raw density), sh [M, 16] from psdf_spherical_harmonics (degree 4) -> x2 [80, M] = [gelu(fd[1:65]); sh^T],
+   one launch.  -1: M < 0 or a NULL pointer; -2: M >= 2^31 */
+int psdf_nerf_head_join(int64_t M, const float* fd, const float* sh, float* x2, void* stream);
+/* replaces: gelu_backward + cat of the same place's backward.  grad_raw [M] (the density's gradient), dX2 [>= 64, M] (row
+   stride M: the colour head's input gradient, its first 64 rows are read), fd [65, M] -> grad_fd [65, M] = [grad_raw;
+   dX2[:64] * gelu'(fd[1:65])] */
+int psdf_nerf_head_join_backward(int64_t M, const float* grad_raw, const float* dX2, const float* fd, float* grad_fd, void*
+    stream);
+
 /* ---- sdf_fit.hip ---- */
 /* Fitting the SDF network to an oriented point cloud (permuto_sdf_py/train_sdf_from_mesh.py, train_4d_sdf.py): the batch of a
    step and the loss tail.  P is the dimension of a position: 3, or 4 with time as the last column.  n_surf rows on the surface

@@ -7,7 +7,8 @@ from . import _lib
 from . import image_eval
 from . import render
 from . import sdf_fit
+from . import nerf_train
 from .encoding import PermutoEncoding, Coarse2Fine
 from .mlp import FusedMLP, LipshitzMLP
 
-__all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval", "render", "sdf_fit"]
+__all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval", "render", "sdf_fit", "nerf_train"]
