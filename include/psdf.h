@@ -76,6 +76,12 @@ int psdf_encode_backward_ws(int pos_dim, int nr_feat, int64_t N, int nr_levels, 
    multiply-adds (encode.hip, combine_runs16), so ONE non-finite upstream gradient makes the gradient of up to 15 other table
    rows handled by the same 16 lanes NaN as well -- a NaN batch is a NaN batch, but more rows show it than carry it. */
 int psdf_encode_backward_level_shares(int* counts, int max_levels);
+/* debug query: how the binning workgroups of the last queue-path call (backward or double backward) that used `workspace` left
+   their LDS scatter caches, per level: kept[l] kept the cache to the end of their walk and handed it to the queues in one
+   round, voted_off[l] switched it off after their first super-tile.  The shape arguments are those of that call.  Waits for
+   `stream`.  Returns the levels written (at most 64 and max_levels); 0 when the queue plan does not apply. */
+int psdf_encode_backward_cache_votes(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const void* workspace,
+    int64_t workspace_bytes, int* kept, int* voted_off, int max_levels, void* stream);
 
 
 /* replaces: permutohedral_encoding `double_backward_from_positions_gpu` (create_graph=True at models.py:245-251) */

@@ -241,11 +241,15 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
 // batch lands on a few dozen table rows, and fp32 atomics to one address serialise (measured: 135 ms for
 // 2M points x 16 levels with plain global atomics).  Each workgroup therefore owns a direct-mapped cache
 // in LDS (tag = table row, F partial sums) that it fills with LDS atomics while it walks its share of the
-// points of one level, and flushes with one global atomic per live entry at the end.  A row whose slot is
-// taken by another row bypasses the cache (plain global atomic), so the structure is exact for any
-// distribution; a workgroup whose hit rate is poor after its first tiles (fine, fully hashed levels)
+// points of one level.  A row whose slot is taken by another row bypasses the cache, so the structure is exact
+// for any distribution; a workgroup whose hit rate is poor after its first tiles (fine, fully hashed levels)
 // switches the cache off for the rest of its walk (vote after its first tile: share of contributions that hit an
 // entry which already existed).
+// The way out depends on the path.  Plain path (batches below the queue plan's threshold): what bypasses the cache is
+// a global float atomic, and `flush` ends the workgroup with one global float atomic per live value.  Queue path: what
+// bypasses the cache goes to the level's queues, and so does the cache itself -- at once when it is voted off
+// (cache_drain_to_queue), in one reservation round at the end of the walk when it is kept (cache_drain_once).  The queue
+// path is thereby left with NO global float atomic except the queue-full fallback of the pushes and drains.
 constexpr uint32_t SC_EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t Q_NONE = 0xFFFFFFFFu;   // "no contribution" in a thread's list of rows (rows are < capacity <= 2^31)
 #if !defined(PSDF_ENC_QSPT)
@@ -373,7 +377,8 @@ struct ScatterCache {
 };
 
 // ----------------------------------------------------------------------------------------- backward
-// grad_lattice[l][row][f] += bary_r * w_l * g[l][f][n]            (LDS-privatised, then fp32 L2 atomics)
+// grad_lattice[l][row][f] += bary_r * w_l * g[l][f][n]            (LDS-privatised; then fp32 L2 atomics on the plain path,
+//                                                                   the queues and encode_bwd_reduce_kernel on the queue path)
 // grad_pos[n][i]          += dL/dpos_i  (chain through barycentric -> elevated -> position)
 // Launch: grid (B, Lt), workgroup b of level l walks point tiles b, b+B, ...
 template <typename SC>
@@ -396,6 +401,11 @@ __device__ __forceinline__ bool cache_vote(SC& sc, int hits, int tries) {
 // RPP*F floats = 128 KiB = one workgroup's LDS.  Slots are reserved per tile with LDS counters and ONE global
 // atomic per (tile, partition); encode_bwd_reduce_kernel then folds every queue into LDS and adds the slice to
 // the gradient with plain stores.  A queue that is full falls back to the global atomic (exact either way).
+// A queue entry is a (row, F values) pair: one contribution, a run of them summed in registers, or -- from a workgroup that is
+// served by its cache -- a drained cache entry, the partial sum of everything that workgroup saw of the row.  The coarse
+// levels' queues hold little else.  Capacity: an entry stands for at least one contribution that was not queued itself, so
+// no queue receives more entries than its rows have contributions, whatever the caches absorb (encode_plan.h sizes it for
+// 1.25 x an even share of all of them).
 struct Queues {
   uint16_t* rows;  // [L, NP, cap]      row index inside the partition
   float* vals;     // [L, NP, cap, F]
@@ -550,10 +560,63 @@ __device__ __forceinline__ void cache_drain_to_queue(SC& sc, const Queues& Q, in
   __syncthreads();
 }
 
+// The scatter cache was KEPT to the end of the walk (coarse and medium levels): its live entries leave through the queues as
+// well, in ONE reservation round for the whole cache.  (cache_drain_to_queue above pushes 256 slots at a time -- SC_SLOTS / 256
+// rounds of three barriers and a returning global atomic per partition: fine once, behind the first tile of a workgroup that goes
+// on working, a serial tail at the end of one.)  Two walks over the tags, nothing kept in registers between them:
+//   count    every thread counts its tagged slots into the per-partition LDS counters
+//   reserve  thread p reserves partition p's segment with one atomic on Q.tails and clears the counter again
+//   write    the second walk takes each entry's place in the segment from the same counters and writes it
+// A tagged slot holds at least one contribution that was therefore NOT queued, so a partition's queue never receives more
+// entries than the level has contributions to that partition's rows -- what queue_plan sizes it for, with its 25 % margin,
+// whether a cache absorbs anything or not.  Past the end of a queue: the float atomic, as everywhere.
+// drained (profile build): where the workgroup adds the number of entries it handed over.
+template <int F, typename SC>
+__device__ __forceinline__ void cache_drain_once(const SC& sc, const Queues& Q, int level, int* q_cnt, int* q_base,
+                                                 float* __restrict__ table_grad, int* drained) {
+  int* q_aux = q_base + Q_MAX_PARTS;
+  const LevelQueues LQ = level_queues<F>(Q, level);
+  // (the last readers of q_cnt are behind a barrier of the last queue_push; q_base / q_aux, which a slow wave may still be
+  // reading there, are written behind the two barriers below)
+  if (threadIdx.x < Q.np) q_cnt[threadIdx.x] = 0;
+  __syncthreads();   // also: every add of the walk has landed in the cache
+  for (int i = threadIdx.x; i < SC::SC_SLOTS; i += PSDF_BLOCK) {
+    const uint32_t row = sc.tags[i];
+    if (row != SC_EMPTY) atomicAdd(&q_cnt[row >> Q.shift], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x < Q.np) {
+    const int c = q_cnt[threadIdx.x];
+    const int base = c ? atomicAdd(&Q.tails[level * Q.np + threadIdx.x], c) : 0;
+    q_base[threadIdx.x] = base;
+    q_aux[threadIdx.x] = (int)threadIdx.x * Q.cap + base;
+    q_cnt[threadIdx.x] = 0;
+    if (drained && c) atomicAdd(drained, c);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < SC::SC_SLOTS; i += PSDF_BLOCK) {
+    const uint32_t row = sc.tags[i];
+    if (row == SC_EMPTY) continue;
+    const int part = row >> Q.shift;
+    const int slot = atomicAdd(&q_cnt[part], 1);
+    float v[F];
+#pragma unroll
+    for (int f = 0; f < F; f++) v[f] = sc.sums[i * F + f];
+    if (q_base[part] + slot < Q.cap) {
+      queue_store<F>(LQ, (uint32_t)(q_aux[part] + slot), row, v);
+    } else {  // queue full: exact fallback
+#pragma unroll
+      for (int f = 0; f < F; f++) atomicAdd(table_grad + (int64_t)row * F + f, v[f]);
+    }
+  }
+}
+
 // Queue mode asks for 5 waves per SIMD: left alone the compiler takes 162 VGPRs (3 waves), told so it needs 96 without a
 // vector spill, and the kernel waits on LDS / gathers for half of its wave cycles (profiles/r02_pmc_sq_encode_bwd.txt), so the
 // extra residents pay: bench batch 0.835 -> 0.79 ms (4 waves: no change; 6 waves spill 13 VGPRs).  The 24-KiB cache of queue
 // mode lets 5 workgroups share a CU's LDS.  (P = 4 and F = 4 would spill a few VGPRs at 5 waves: they ask for 4.)
+// A queue-mode workgroup ends by handing what is left in its cache to the queues (cache_drain_once: two walks over the tags,
+// nothing held in registers between them, so the budget above stands) -- it issues no global float atomic unless a queue is full.
 // DBL = true: the DOUBLE backward's lattice scatter through the same machinery (see encode_dbl_bwd_kernel for the maths): the
 // coefficient of vertex r is q_r (the directional derivative of its barycentric along u = dd_positions) instead of bary_r, and
 // the kernel also writes grad_grad_sliced = sum_r q_r w lattice[row_r] (a gather of the rows it has just computed; skipped
@@ -857,16 +920,32 @@ __global__ void __launch_bounds__(PSDF_BLOCK, QUEUE ? ((P <= 3 && F == 2) ? PSDF
       if (QUEUE && !use_cache) cache_drain_to_queue<F>(sc, Q, level, q_cnt, q_base, grad_lattice + tbase);
     }
   }
-  // (a cache that was switched off in queue mode has been drained and its LDS re-used: nothing to flush)
-  if (LATTICE && !(QUEUE && !use_cache)) sc.flush(grad_lattice + tbase);
+  // The way out of the cache.  Queue mode: through the queues (a cache that was switched off has been drained and its LDS
+  // re-used; one that was kept is drained here, in one round).  Plain mode: one global float atomic per live value.
+  if (LATTICE) {
+    if (QUEUE) {
+      if (use_cache) {
+#if defined(PSDF_ENC_PROFILE)
+        int* const drained = Q.tails + L * Q.np + 192 + level;
+#else
+        int* const drained = nullptr;
+#endif
+        cache_drain_once<F>(sc, Q, level, q_cnt, q_base, grad_lattice + tbase, drained);
+      }
+    } else {
+      sc.flush(grad_lattice + tbase);
+    }
+  }
   plan_report();
+  // How the workgroup left (psdf_encode_backward_cache_votes, a debug query): one word per level behind the queue counters,
+  // zeroed with them -- low half: workgroups that kept their cache to the end, high half: those that voted it off.
+  if (QUEUE && LATTICE && threadIdx.x == 0 && level < 64) atomicAdd(Q.tails + L * Q.np + 128 + level, use_cache ? 1 : 0x10000);
 #if defined(PSDF_ENC_PROFILE)
   if (QUEUE && threadIdx.x == 0) {   // per-level duration of the workgroups (wall clock ticks), into the tail of the queue counters
     const long long dt = (long long)wall_clock64() - psdf_prof_t0;
     int* prof = Q.tails + L * Q.np;
     atomicMax(&prof[level], (int)dt);
     atomicAdd(&prof[64 + level], (int)(dt >> 6));
-    atomicAdd(&prof[128 + level], use_cache ? 1 : 0);
   }
 #endif
 }
@@ -1436,13 +1515,13 @@ Queues queue_carve(void* ws, const plan::QueuePlan& p) {
   char* b = (char*)ws;
   return Queues{(uint16_t*)b, (float*)(b + p.rows_bytes), (int*)(b + p.rows_bytes + p.vals_bytes), p.cap, p.np, p.shift};
 }
-// false: the plain path runs.  Otherwise Q is carved and its counters (and `also_zeroed` bytes behind them) are zeroed on the stream.
-bool queue_begin(int pos_dim, int nr_feat, const EncCall& c, bool wanted, void* ws, int64_t ws_bytes, size_t also_zeroed, Queues& Q,
-                 hipError_t& e) {
+// false: the plain path runs.  Otherwise Q is carved and its counters are zeroed on the stream, together with the 1024 bytes of
+// slots behind them (the plan always holds them: per-level cache votes, and the profile build's durations and drain counts).
+bool queue_begin(int pos_dim, int nr_feat, const EncCall& c, bool wanted, void* ws, int64_t ws_bytes, Queues& Q, hipError_t& e) {
   const plan::QueuePlan p = (wanted && ws) ? queue_plan(pos_dim, nr_feat, c.N, c.nr_levels, c.capacity) : plan::QueuePlan{};
   if (p.bytes == 0 || ws_bytes < p.bytes) return false;
   Q = queue_carve(ws, p);
-  e = hipMemsetAsync(Q.tails, 0, (size_t)c.nr_levels * Q.np * sizeof(int) + also_zeroed, c.stream);
+  e = hipMemsetAsync(Q.tails, 0, (size_t)c.nr_levels * Q.np * sizeof(int) + plan::Q_SLOT_BYTES, c.stream);
   return true;
 }
 
@@ -1584,16 +1663,19 @@ void enc_profile_report(const EncCall& c, int pos_dim, const Queues& Q, unsigned
   static int calls = 0;
   if (++calls != 8) return;
   (void)hipStreamSynchronize(c.stream);
-  int prof[192];
+  int prof[256];   // [0, 64) longest workgroup, [64, 128) sum of durations / 64, [128, 192) caches kept, [192, 256) entries drained
   (void)hipMemcpy(prof, Q.tails + c.nr_levels * Q.np, sizeof(prof), hipMemcpyDeviceToHost);
   std::vector<int> tails((size_t)c.nr_levels * Q.np);
   (void)hipMemcpy(tails.data(), Q.tails, tails.size() * sizeof(int), hipMemcpyDeviceToHost);
   for (int l = 0; l < c.nr_levels; l++) {
-    long long queued = 0;
-    for (int q = 0; q < Q.np; q++) queued += tails[(size_t)l * Q.np + q];
+    // the tails count every entry of the level's queues: the contributions pushed during the walk and, apart from them, the
+    // cache entries (partial sums of many contributions each) that the workgroups which kept their cache drained at the end
+    long long entries = 0;
+    for (int q = 0; q < Q.np; q++) entries += tails[(size_t)l * Q.np + q];
+    const long long queued = entries - prof[192 + l];
     fprintf(stderr, "[enc-profile] level %2d: max %8d ticks, mean %8.0f ticks, cache kept by %d of %u workgroups, queued %lld of %lld "
-            "contributions (%.1f %%)\n", l, prof[l], 64.0 * prof[64 + l] / gx, prof[128 + l], gx, queued,
-            (long long)c.N * (pos_dim + 1), 100.0 * queued / ((double)c.N * (pos_dim + 1)));
+            "contributions (%.1f %%), drained %d cache entries\n", l, prof[l], 64.0 * prof[64 + l] / gx, prof[128 + l] & 0xffff, gx, queued,
+            (long long)c.N * (pos_dim + 1), 100.0 * queued / ((double)c.N * (pos_dim + 1)), prof[192 + l]);
   }
 }
 #endif
@@ -1740,6 +1822,27 @@ int psdf_encode_backward_level_shares(int* counts, int max_levels) {
   return n;
 }
 
+// How the binning workgroups of the last queue-path call that used `workspace` left their scatter caches (debug query; the
+// arguments are those of that call): kept[l] workgroups of level l kept the cache to the end of their walk and drained it into
+// the queues in one round, voted_off[l] switched it off after their first super-tile.  Waits for `stream`.  Returns the number of
+// levels written (at most 64 and max_levels), 0 when the queue plan does not apply to these arguments.
+int psdf_encode_backward_cache_votes(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const void* workspace,
+                                     int64_t workspace_bytes, int* kept, int* voted_off, int max_levels, void* stream) {
+  const plan::QueuePlan p = queue_plan(pos_dim, nr_feat, N, nr_levels, capacity);
+  if (!workspace || !kept || !voted_off || p.bytes == 0 || workspace_bytes < p.bytes) return 0;
+  int words[64];
+  const int n = nr_levels < 64 ? (nr_levels < max_levels ? nr_levels : max_levels) : (max_levels < 64 ? max_levels : 64);
+  if (n <= 0) return 0;
+  const Queues Q = queue_carve(const_cast<void*>(workspace), p);
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return 0;
+  if (hipMemcpy(words, Q.tails + (size_t)nr_levels * Q.np + 128, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  for (int l = 0; l < n; l++) {
+    kept[l] = words[l] & 0xffff;
+    voted_off[l] = (int)((uint32_t)words[l] >> 16);
+  }
+  return n;
+}
+
 // grad_lattice / grad_positions must be zero-initialised by the caller (or hold a running sum to add to);
 // either may be NULL to skip that gradient.  workspace: device scratch of at least
 // psdf_encode_backward_workspace_bytes() bytes (contents undefined on entry and exit) or NULL.
@@ -1755,12 +1858,7 @@ int psdf_encode_backward_ws(int pos_dim, int nr_feat, int64_t N, int nr_levels, 
   if (!grad_positions) c.Lt = nr_levels;   // the pseudo-levels of the concatenated points carry a position gradient only
   Queues Q{};
   hipError_t e = hipSuccess;
-#if defined(PSDF_ENC_PROFILE)
-  const size_t profile_slots = 1024;
-#else
-  const size_t profile_slots = 0;
-#endif
-  const bool use_queue = queue_begin(pos_dim, nr_feat, c, grad_lattice, workspace, workspace_bytes, profile_slots, Q, e);
+  const bool use_queue = queue_begin(pos_dim, nr_feat, c, grad_lattice, workspace, workspace_bytes, Q, e);
   if (e != hipSuccess) return (int)e;
   const int rc = dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
     return launch_bwd(p, f, c, grad_sliced, grad_lattice, grad_positions, use_queue ? &Q : nullptr);
@@ -1813,7 +1911,7 @@ int psdf_encode_double_backward_ws(int pos_dim, int nr_feat, int64_t N, int nr_l
     return PSDF_ERR_ARG;
   Queues Q{};
   hipError_t e = hipSuccess;
-  if (queue_begin(pos_dim, nr_feat, c, grad_lattice, workspace, workspace_bytes, 0, Q, e)) {
+  if (queue_begin(pos_dim, nr_feat, c, grad_lattice, workspace, workspace_bytes, Q, e)) {
     if (e != hipSuccess) return (int)e;
     return launched(dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
       return launch_dbl_queue(p, f, c, dd_positions, grad_sliced, grad_lattice, grad_grad_sliced, grad_sliced_direct, Q);

@@ -18,8 +18,10 @@ inline long long env_long(const char* name, long long dflt) { const char* v = ge
 // ------------------------------------------------------------------------------------------ queue plan
 constexpr int Q_MAX_PARTS = 64;   // partitions of a level's table (the binning kernel keeps four counters per partition in LDS)
 
+constexpr int Q_SLOT_BYTES = 1024;   // behind the tails: one word per level of cache votes; durations and drain counts (profile build)
+
 // bytes == 0: the path does not apply (small batch, table too large for Q_MAX_PARTS partitions, queues past the kernels' 32-bit
-// offsets) and every other field is 0.  The workspace is [rows | vals | tails | 1024 B of profile slots (variant builds)].
+// offsets) and every other field is 0.  The workspace is [rows | vals | tails | Q_SLOT_BYTES of per-level slots].
 struct QueuePlan {
   int cap, np, shift;   // entries per (level, partition) queue; partitions; rows per partition = 1 << shift
   int64_t rows_bytes, vals_bytes, tails_bytes, bytes;
@@ -50,7 +52,7 @@ inline QueuePlan queue_plan(int pos_dim, int nr_feat, int64_t N, int nr_levels, 
   const auto round256 = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
   const int64_t entries = (int64_t)nr_levels * np * cap;
   QueuePlan p{(int)cap, np, shift, round256(entries * 2), round256(entries * nr_feat * 4), round256((int64_t)nr_levels * np * 4), 0};
-  p.bytes = p.rows_bytes + p.vals_bytes + p.tails_bytes + 1024;
+  p.bytes = p.rows_bytes + p.vals_bytes + p.tails_bytes + Q_SLOT_BYTES;
   return p;
 }
 
