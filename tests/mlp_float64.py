@@ -6,6 +6,10 @@ Per-entry metric: |ours - f64| / S with S the entry's own absolute sum in float6
 blow up where a sum cancels): dW_l: |dZ_l|^T |H_{l-1}|, db_l: sum |dZ_l|, dX: |dZ_1| |W_1|, Y: |h_{L-1}| |W_L|^T + |b_L|.  An entry
 whose S is 0 has no non-zero term at all and must be exactly 0.
 
+Below the baseline net: the float64 evaluator of the DOUBLE backward (f64_double_backward, with S of the last dot product only),
+its input families and its case lists, for tests/test_mlp_double_backward_float64.py and
+tests/test_gpu_mlp_double_backward_float64.py.
+
 No test in here; everything is generated on the CPU from seeded generators, so the host tests and the GPU tests see the same
 numbers."""
 import torch
@@ -89,10 +93,13 @@ def plain_inputs(K0, N, gen):
     return x
 
 
-def sdf_net(K0, seed):
-    """the four torch.nn.Linear of K0-64-64-64-1 with biases ~ N(0, 0.1) (as tests/test_gpu_mlp.py makes its split nets)"""
+def sdf_net(K0, seed, out=1, hidden=64):
+    """the four torch.nn.Linear of K0-64-64-64-1 with biases ~ N(0, 0.1) (as tests/test_gpu_mlp.py makes its split nets);
+    out / hidden: the other widths of the double-backward rows (hidden: one width, or the three of a ragged net)"""
     torch.manual_seed(seed)
-    dims = [K0, 64, 64, 64, 1]
+    hidden = [hidden] * 3 if isinstance(hidden, int) else list(hidden)
+    assert len(hidden) == 3
+    dims = [K0] + hidden + [out]
     lin = [torch.nn.Linear(dims[i], dims[i + 1]) for i in range(4)]
     for l in lin:
         torch.nn.init.normal_(l.bias, 0.0, 0.1)
@@ -152,3 +159,220 @@ def geometry_case(K0, N):
     lin = sdf_net(K0, seed)
     x = sdf_inputs(K0, N, 1e-2, 0, gen) if K0 == 36 else plain_inputs(K0, N, gen)
     return lin, x, sdf_dy(N, "ordinary", gen, misses=False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the DOUBLE backward (mlp_dbl_bwd_kernel of csrc/mlp_bwd.hip: psdf_mlp_double_backward, psdf_mlp_double_backward_plus), shared by
+# tests/test_mlp_double_backward_float64.py (host) and tests/test_gpu_mlp_double_backward_float64.py
+
+DBL_TENSORS = ("dX2", "dW1", "db1", "dW2", "db2", "dW3", "db3", "dW4", "db4")
+# what a mutation of the evaluator changes (tests/test_mlp_double_backward_float64.py measures each against the unmutated one)
+DBL_MUTATIONS = [("drop_c", 1), ("drop_c", 2), ("drop_c", 3), ("a_for_c", 1), ("a_for_c", 2), ("a_for_c", 3), ("drop_u1V", 0),
+                 ("drop_dY2H3", 0), ("drop_last_sample", 0), ("dY2_without_a3", 0)]
+
+
+def _gelu_terms64(z):
+    """float64 z -> (gelu, a = gelu', c = gelu'' = phi(z) (2 - z^2))"""
+    cdf = 0.5 * (1 + torch.erf(z / 2 ** 0.5))
+    pdf = torch.exp(-0.5 * z * z) / (2 * torch.pi) ** 0.5
+    return z * cdf, cdf + z * pdf, pdf * (2 - z * z)
+
+
+def f64_double_backward(lin, x, dy, v, dy2=None, mutate=None):
+    """float64, by hand and without autograd, in the notation of the kernel's comment (four layers, three hidden):
+        H_0 = X;  Z_l = H_{l-1} W_l^T + b_l;  H_l = gelu(Z_l), a_l = gelu'(Z_l), c_l = gelu''(Z_l)  (l = 1..3);  Y = Z_4
+        u_4 = dY;  q_l = u_{l+1} W_{l+1};  u_l = a_l * q_l  (l = 3..1)                                  [dX = u_1 W_1]
+        objective <dX, V> + <Y, dY2>
+        du_1 = V W_1^T;  da_l = du_l * q_l;  dq_l = du_l * a_l;  du_{l+1} = dq_l W_{l+1}^T
+        dz_3 = da_3 * c_3 + (dY2 W_4) * a_3;  dz_l = (dz_{l+1} W_{l+1}) * a_l + da_l * c_l;  dX2 = dz_1 W_1
+        dW_1 = u_1^T V + dz_1^T X;  dW_{l+1} = u_{l+1}^T dq_l + dz_{l+1}^T H_l (l = 1, 2);  dW_4 = dY^T dq_3 + dY2^T H_3
+        db_l = sum_n dz_l (l = 1..3);  db_4 = sum_n dY2
+    dy None: the unit gradient of output 0; dy2 None: absent.  -> (gradients {name: tensor}, absolute sums S {name: tensor}, Z
+    [Z_1 .. Z_4]).  S is the absolute sum of the LAST dot product of an entry only, its operands at their float64 values.
+    mutate (kind, layer): one deliberate defect, see DBL_MUTATIONS."""
+    kind, ml = mutate if mutate else (None, 0)
+    W = [None] + [l.weight.detach().double() for l in lin]          # 1-based, as in the comment
+    b = [None] + [l.bias.detach().double() for l in lin]
+    assert len(W) == 5
+    X, V = x.double(), v.double()
+    N = X.shape[0]
+    if dy is None:
+        dY = torch.zeros(N, W[4].shape[0], dtype=torch.float64, device=X.device)
+        dY[:, 0] = 1.0
+    else:
+        dY = dy.double()
+    dY2 = torch.zeros_like(dY) if dy2 is None else dy2.double()
+    H, Z, a, c = [X], [None], [None], [None]
+    for l in (1, 2, 3):
+        Z.append(H[l - 1] @ W[l].t() + b[l])
+        h, al, cl = _gelu_terms64(Z[l])
+        H.append(h)
+        a.append(al)
+        c.append(al if (kind == "a_for_c" and ml == l) else torch.zeros_like(cl) if (kind == "drop_c" and ml == l) else cl)
+    Z.append(H[3] @ W[4].t() + b[4])
+    u, q = [None] * 5, [None] * 4
+    u[4] = dY
+    for l in (3, 2, 1):
+        q[l] = u[l + 1] @ W[l + 1]
+        u[l] = a[l] * q[l]
+    du, da, dq = [None] * 5, [None] * 4, [None] * 4
+    du[1] = V @ W[1].t()
+    for l in (1, 2, 3):
+        da[l] = du[l] * q[l]
+        dq[l] = du[l] * a[l]
+        if l < 3:
+            du[l + 1] = dq[l] @ W[l + 1].t()
+    dz = [None] * 4
+    dh3 = dY2 @ W[4]
+    dz[3] = da[3] * c[3] + (dh3 if kind == "dY2_without_a3" else dh3 * a[3])
+    for l in (2, 1):
+        dz[l] = (dz[l + 1] @ W[l + 1]) * a[l] + da[l] * c[l]
+    # the sums over the samples: m drops the last sample of the (partial) last 16-sample tile from them (its dX2 row stays)
+    m = torch.ones(N, 1, dtype=torch.float64, device=X.device)
+    if kind == "drop_last_sample":
+        m[N - 1] = 0.0
+    T = lambda t: (t * m).t()
+    A = torch.abs
+    g, S = {}, {}
+    g["dX2"], S["dX2"] = dz[1] @ W[1], A(dz[1]) @ A(W[1])
+    uV = torch.zeros_like(W[1]) if kind == "drop_u1V" else T(u[1]) @ V
+    g["dW1"], S["dW1"] = uV + T(dz[1]) @ X, A(u[1]).t() @ A(V) + A(dz[1]).t() @ A(X)
+    for l in (1, 2):
+        g["dW%d" % (l + 1)] = T(u[l + 1]) @ dq[l] + T(dz[l + 1]) @ H[l]
+        S["dW%d" % (l + 1)] = A(u[l + 1]).t() @ A(dq[l]) + A(dz[l + 1]).t() @ A(H[l])
+    y2h3 = torch.zeros_like(W[4]) if kind == "drop_dY2H3" else T(dY2) @ H[3]
+    g["dW4"], S["dW4"] = T(dY) @ dq[3] + y2h3, A(dY).t() @ A(dq[3]) + A(dY2).t() @ A(H[3])
+    for l in (1, 2, 3):
+        g["db%d" % l], S["db%d" % l] = (dz[l] * m).sum(0), A(dz[l]).sum(0)
+    g["db4"], S["db4"] = (dY2 * m).sum(0), A(dY2).sum(0)
+    return g, S, Z[1:]
+
+
+def double_backward_autograd(lin, x, dy, v, dy2=None, dtype=torch.float64):
+    """the same gradients by unmodified torch autograd of <d y / d x . dY, V> + <Y, dY2> with create_graph=True, in `dtype`
+    (float64: what pins the evaluator; float32: the figure t of the GPU bars) -> {name: tensor}"""
+    Ws = [l.weight.detach().to(dtype).requires_grad_(True) for l in lin]
+    bs = [l.bias.detach().to(dtype).requires_grad_(True) for l in lin]
+    X = x.detach().to(dtype).requires_grad_(True)
+    h = X
+    for i in range(4):
+        h = torch.nn.functional.linear(h, Ws[i], bs[i])
+        if i < 3:
+            h = torch.nn.functional.gelu(h)
+    if dy is None:
+        dY = torch.zeros_like(h)
+        dY[:, 0] = 1.0
+    else:
+        dY = dy.to(dtype)
+    (gx,) = torch.autograd.grad(h, X, dY, create_graph=True)
+    obj = (gx * v.to(dtype)).sum()
+    if dy2 is not None:
+        obj = obj + (h * dy2.to(dtype)).sum()
+    outs = torch.autograd.grad(obj, [X] + Ws + bs, allow_unused=True)
+    outs = [o if o is not None else torch.zeros_like(t) for o, t in zip(outs, [X] + Ws + bs)]
+    g = {"dX2": outs[0]}
+    for l in range(4):
+        g["dW%d" % (l + 1)], g["db%d" % (l + 1)] = outs[1 + l], outs[5 + l]
+    return g
+
+
+def sdf_layout(K0):
+    """the widths an encoding of this project produces for the SDF nets (8, 16 and 24 levels); the others get plain_inputs"""
+    return K0 in (20, 36, 52)
+
+
+def dbl_v(K0, N, kind, closed_levels, gen, misses=False, layout=True):
+    """[N, K0] fp32, the upstream gradient of dX as the encoding's double backward hands it over.  "ordinary": randn; "decades":
+    randn * 10^(-6 u) per sample.  With the encoding's layout the columns of the closed levels and the zero pad column are
+    exactly 0; misses: 1 row in 16 is exactly 0 (the rows of sdf_dy and dbl_dy2)."""
+    assert kind in ("ordinary", "decades"), kind
+    v = torch.randn(N, K0, generator=gen)
+    if kind == "decades":
+        v = v * 10.0 ** (-6.0 * torch.rand(N, 1, generator=gen))
+    if layout:
+        L = sdf_levels(K0)
+        if closed_levels:
+            v[:, 2 * (L - closed_levels):2 * L] = 0.0
+        v[:, K0 - 1] = 0.0
+    if misses:
+        v[5::16] = 0.0
+    return v
+
+
+def dbl_dy2(N, out, gen, misses=False):
+    """[N, out] fp32, the upstream gradient of the outputs that the plus form folds in: randn * 0.3, the missed rows exactly 0"""
+    g = torch.randn(N, out, generator=gen) * 0.3
+    if misses:
+        g[5::16] = 0.0
+    return g
+
+
+class DblCase:
+    """one case of the double backward.  dims [K0, d1, d2, d3, out]; lattice 1e-5 closes six levels, 1e-2 none (only where
+    sdf_layout(K0)); v "ordinary" / "decades"; misses; dy "unit" (None is passed: the production form) / "randn"; plus: with dY2;
+    tails: W_1 and b_1 times TAILS_SCALE"""
+
+    def __init__(self, dims, N, lattice=1e-2, v="ordinary", misses=False, dy="unit", plus=False, tails=False):
+        self.dims, self.N, self.lattice, self.v, self.misses, self.dy, self.plus, self.tails = \
+            list(dims), N, lattice, v, misses, dy, plus, tails
+
+    def key(self):
+        return (tuple(self.dims), self.N, self.lattice, self.v, self.misses, self.dy, self.plus, self.tails)
+
+    def __repr__(self):
+        return "%s%s N=%d lattice=%g V=%s%s dY=%s%s" % ("-".join(map(str, self.dims)), " plus" if self.plus else "", self.N,
+                                                       self.lattice, self.v, "+misses" if self.misses else "", self.dy,
+                                                       " tails" if self.tails else "")
+
+    def at(self, N):
+        """the same family at another batch"""
+        return DblCase(self.dims, N, self.lattice, self.v, self.misses, self.dy, self.plus, self.tails)
+
+    def closed(self):
+        return 6 if (self.lattice == 1e-5 and sdf_layout(self.dims[0])) else 0
+
+    def make(self):
+        """-> (lin, x [N, K0], dy [N, out] or None, v [N, K0], dy2 [N, out] or None), seeded by the case itself"""
+        import zlib
+        seed = zlib.crc32(repr(self.key()).encode())
+        gen = torch.Generator().manual_seed(seed)
+        K0, out, N = self.dims[0], self.dims[4], self.N
+        lin = sdf_net(K0, seed, out=out, hidden=self.dims[1:4])
+        if self.tails:
+            with torch.no_grad():
+                lin[0].weight.mul_(TAILS_SCALE)
+                lin[0].bias.mul_(TAILS_SCALE)
+        layout = sdf_layout(K0)
+        x = sdf_inputs(K0, N, self.lattice, self.closed(), gen) if layout else plain_inputs(K0, N, gen)
+        v = dbl_v(K0, N, self.v, self.closed(), gen, self.misses, layout)
+        dy = None if self.dy == "unit" else torch.randn(N, out, generator=gen)
+        dy2 = dbl_dy2(N, out, gen, self.misses) if self.plus else None
+        return lin, x, dy, v, dy2
+
+
+# "tails": pre-activations far out in the GELU tails, where 1 + erf cancels, __expf is at its worst and 2 - z^2 is large and
+# negative.  The inputs of the encoding's layout are bounded (|point| <= 0.7, lattice features of 1e-2), so a factor of 4 on W_1
+# and b_1 reaches max |z_1| = 1.6 .. 1.9 only (measured on these seeds, 0.04 .. 0.4 % of z_1 near +-sqrt 2); 20 reaches
+# 8.0 .. 9.3 with 2.8 .. 3.2 % near +-sqrt 2, which is what the host test asserts of the drawn cases (>= 6, >= 1 %)
+TAILS_SCALE = 20.0
+DBL_BASE, DBL_REF = [36, 64, 64, 64, 1], [52, 32, 32, 32, 33]      # the two production nets; DBL_REF runs in the plus form
+N_DBL = 16_423                       # 256 x 4 x 16 + 39: two waves take a second tile, the last tile is partial
+# every DBL row of PSDF_MLP16_ROWS (csrc/mlp_dispatch.h) that the library launches, the PLUS rows with and without dY2; ragged
+# widths; the final-dot rows with 3 and 4 outputs and a randn dY; one PLUS row with a randn dY
+DBL_ROW_CASES = [DblCase(d, N_DBL) for d in ([36, 64, 64, 64, 1], [52, 32, 32, 32, 1], [36, 32, 32, 32, 1],
+                                             [20, 32, 32, 32, 1], [52, 32, 32, 32, 33], [36, 32, 32, 32, 33])] + \
+                [DblCase(d, N_DBL, plus=True) for d in ([52, 32, 32, 32, 33], [36, 32, 32, 32, 33], [51, 30, 32, 28, 40])] + \
+                [DblCase(d, N_DBL, dy="randn") for d in ([35, 64, 64, 64, 3], [44, 64, 64, 64, 4])] + \
+                [DblCase([52, 32, 32, 32, 33], N_DBL, dy="randn", plus=True)]
+# no fused double backward: row (2, 4, 4, 4, 1) has DBL = 0; row (4, 4, 4, 4, 1) has DBL = 1, but its launch (weight images of
+# 49..64 inputs, 100 096 bytes, plus transpose buffer and four staging tiles of each of four waves, 70 144 bytes) is past the
+# 163 840 bytes of LDS a launch may use, so
+# psdf_mlp_supported declines it (LDS_DECLINED of tests/test_dispatch_tables.py): built, never launched
+DBL_UNSUPPORTED = [[20, 64, 64, 64, 1], [52, 64, 64, 64, 1]]
+DBL_NUMERICS_CASES = [DblCase(d, N_DBL, lattice, v, misses, plus=d is DBL_REF, tails=tails)
+                      for d in (DBL_BASE, DBL_REF)
+                      for lattice, tails in ((1e-5, False), (1e-2, False), (1e-2, True))
+                      for v, misses in (("ordinary", False), ("decades", True))]
+# 1: a single sample; 17: one tile + 1; 63 / 64 / 65: one workgroup's four tiles -1 / exact / +1; 16 423: see N_DBL; 32 807: three
+# waves take a third tile, so the two-slot prefetch returns to its first slot
+DBL_GEOMETRY_CASES = [DblCase(d, N, plus=d is DBL_REF) for d in (DBL_BASE, DBL_REF) for N in (1, 17, 63, 64, 65, N_DBL, 32_807)]
