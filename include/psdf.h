@@ -323,6 +323,17 @@ int psdf_encode_backward_positions_masked(int pos_dim, int nr_feat, int64_t N, i
     positions, const float* lattice, const float* scale_factor, const float* shifts, const float* window, int
     concat_points, float points_scaling, const float* grad_sliced, const uint8_t* skip, float* grad_positions, void*
     stream);
+/* the same with the caller's scratch for the per-level-group partial sums: they are added in group order, never with float
+   atomics, so the same inputs give the same bits on every call, also while `stream` is being captured into a graph (where the
+   entry above has no scratch of its own and takes the atomic form).  Outside a capture the bits are the entry's above.
+   replaces: nothing new in the reference (the same get_sdf_and_gradient); what it adds is a captured trace whose normals equal
+   the eager trace's bit for bit (box_trace.py).  workspace: psdf_encode_backward_positions_workspace_bytes() bytes (host only;
+   0: none needed, workspace may be NULL); a smaller or missing workspace: -1 */
+int64_t psdf_encode_backward_positions_workspace_bytes(int pos_dim, int nr_feat, int64_t N, int nr_levels, int concat_points);
+int psdf_encode_backward_positions_masked_ws(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity, const float*
+    positions, const float* lattice, const float* scale_factor, const float* shifts, const float* window, int
+    concat_points, float points_scaling, const float* grad_sliced, const uint8_t* skip, float* grad_positions, void*
+    workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- mlp_bwd.hip ---- */
 /* replaces: autograd backward of the same evaluators (dX, dW_l, db_l in one launch; forward recomputed from X).
@@ -868,6 +879,43 @@ int psdf_sdf_fit_loss(int P, int64_t n_surf, int64_t n_off, const float* sdf, co
 int psdf_trace_frame_resolve(int nr_rays, int nr_valid, const int* slot, const float* origins, const float* dirs, const float*
     pos, const float* gradients, const float* rgb, const float* rot_cam_world, int H, int W, int64_t pixel_first, float* rgb_img,
     float* normals_img, float* normals_cam_img, float* weights_sum_img, float* depth_img, void* stream);
+
+/* ---- box_trace.hip ---- */
+/* Sphere tracing inside an axis-aligned box without an occupancy grid, one slot per ray, and the image planes of such a view.
+   The box comes as HOST triples computed by the caller in float32 in the reference's order (permuto_sdf_py/utils/aabb.py:15-25,
+   48-49): box_min = -sizes / 2 + translation, box_max = sizes - sizes / 2 + translation (the intersection); translation and
+   half = sizes / 2 (the inside test).  origins, dirs [nr_rays, 3]; points are rows of `stride` floats, stride 3, or 4 with the
+   time in column 3; flags are bytes.  The entries allocate nothing and never synchronise; nr_rays = 0 returns 0 without a
+   launch; -1 for nr_rays < 0, a stride other than 3 or 4, or a NULL required pointer. */
+/* replaces: AABB.ray_intersection (permuto_sdf_py/utils/aabb.py:47-100), operation for operation: IEEE division per axis (a
+   direction component of +-0 included), the swap, lo / hi from -+1e10, the two miss conditions, both depths 0 on a miss, lo
+   clamped at 0, origin + t * dir as a product and a sum -> t_entry, t_exit [nr_rays], pts_entry, pts_exit [nr_rays, 3], hit
+   [nr_rays] */
+int psdf_box_ray_intersection(int nr_rays, const float* box_min, const float* box_max, const float* origins, const float* dirs,
+    float* t_entry, float* t_exit, float* pts_entry, float* pts_exit, uint8_t* hit, void* stream);
+/* replaces: the start of sphere_trace without an occupancy grid (permuto_sdf_py/utils/sdf_utils.py:122, 136-144): pts [nr_rays,
+   stride] <- the entry point (the origin for a ray that misses the box), column 3 <- time[0] with stride 4 (time: DEVICE pointer
+   to one float, read by the kernel: a captured launch follows it; may be NULL with stride 3); converged = no_hit <- !hit (a ray
+   that misses is held as converged and never evaluated; the reference traces it from the camera centre) */
+int psdf_box_trace_begin(int nr_rays, int stride, const float* box_min, const float* box_max, const float* origins, const float*
+    dirs, const float* time, float* pts, uint8_t* converged, uint8_t* no_hit, void* stream);
+/* replaces: one iteration of that loop after the network (sdf_utils.py:167-185) with check_point_inside_primitive
+   (aabb.py:28-42), for the rays with converged == 0: p <- p + (d * sdf) * multiplier; converged |= |sdf| < thresh (the SDF from
+   before the move) || !(p - translation strictly between -half and half on all three axes).  Column 3 is never touched; rays
+   with converged != 0 are not touched at all */
+int psdf_box_trace_step(int nr_rays, int stride, const float* translation, const float* half, const float* dirs, const float* sdf,
+    float multiplier, float thresh, float* pts, uint8_t* converged, void* stream);
+/* replaces: filter_unconverged_points (sdf_utils.py:221-231), F.normalize and the convergence mask of
+   permuto_sdf_py/experiments/visualization/vis_4d_sdf.py:106-118, as planes, for the chunk [pixel_first, pixel_first + nr_rays)
+   of an H x W frame.  A ray is covered iff !no_hit && sdf_end < coverage_thresh (a signed compare; a NaN is not covered).
+   Written at pixel pixel_first + ray, for a covered ray / any other: normals_img [3, H, W] <- g / max(|g|, 1e-12), g =
+   gradients[ray, 0:3] (rows of `stride` floats, as pts) / 0; normals_cam_img [3, H, W] or NULL <- normalize(R n), R =
+   rot_cam_world (device, 9 floats, row major) / 0; weights_sum_img [1, H, W] <- 1 / 0; depth_img [1, H, W] <- ((px - ox) dx +
+   (py - oy) dy) + (pz - oz) dz / 0.  Every pixel of the range is written once, nothing outside it.  Also -1 for an extent < 1,
+   a range outside the frame or camera normals without the rotation; -2 for H W >= 2^31 */
+int psdf_box_trace_resolve(int nr_rays, int stride, const float* origins, const float* dirs, const float* pts, const float*
+    sdf_end, const float* gradients, const uint8_t* no_hit, float coverage_thresh, const float* rot_cam_world, int H, int W,
+    int64_t pixel_first, float* normals_img, float* normals_cam_img, float* weights_sum_img, float* depth_img, void* stream);
 
 /* ---- frame_rays.hip, frame_composite.hip ---- */
 /* A held-out view rendered volumetrically, a chunk of pixels at a time, into planar [3, H, W] / [1, H, W] fp32 images on the

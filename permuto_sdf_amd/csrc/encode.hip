@@ -1466,7 +1466,8 @@ int encode_forward_impl(int pos_dim, int nr_feat, int64_t N, int nr_levels, int 
 // The level-group kernel + the slab reduction when stream-ordered scratch is available (not while a graph is being captured:
 // there the float-atomic form runs), PSDF_ENC_POS_ATOMICS=1 forces the atomic form (A/B).
 template <int P, int F, int POS_LPB>
-void launch_bwd_pos_lpb(const EncCall& c, const float* grad_sliced, const unsigned char* skip, float* grad_positions, bool capturing) {
+void launch_bwd_pos_lpb(const EncCall& c, const float* grad_sliced, const unsigned char* skip, float* grad_positions, bool capturing,
+                        float* caller_slabs = nullptr) {
   static const bool force_atomics = env_int("PSDF_ENC_POS_ATOMICS", 0) != 0;
   const int groups = (c.Lt + POS_LPB - 1) / POS_LPB;
   // The slabs are per-stream scratch that is never handed back: capped (PSDF_ENC_POS_SLAB_MAX_MB, default 256 MiB = 1.7 M points
@@ -1475,7 +1476,9 @@ void launch_bwd_pos_lpb(const EncCall& c, const float* grad_sliced, const unsign
   static const size_t slab_cap = (size_t)plan::env_long("PSDF_ENC_POS_SLAB_MAX_MB", 256) << 20;
   const size_t slab_bytes = (size_t)groups * c.N * P * sizeof(float);
   const bool use_slabs = groups > 1 && !force_atomics && !capturing && slab_bytes <= slab_cap;
-  float* slabs = use_slabs ? (float*)psdf::stream_scratch(slab_bytes, c.stream) : nullptr;
+  // caller_slabs: groups * N * P floats of the caller's (psdf_encode_backward_positions_masked_ws: the slab form whatever the
+  // stream's capture state)
+  float* slabs = caller_slabs ? (groups > 1 ? caller_slabs : nullptr) : use_slabs ? (float*)psdf::stream_scratch(slab_bytes, c.stream) : nullptr;
   const auto pos_kernel = [&](auto kern, float* out) {
     hipLaunchKernelGGL(kern, dim3(psdf_blocks(c.N, PSDF_BLOCK), groups), dim3(PSDF_BLOCK), 0, c.stream, c.N, c.nr_levels, c.Lt,
                        (uint32_t)c.capacity, psdf::enc_conv_state(), c.positions, c.lattice, c.scale_factor, c.shifts, c.window,
@@ -1890,6 +1893,44 @@ int psdf_encode_backward_positions_masked(int pos_dim, int nr_feat, int64_t N, i
     return PSDF_ERR_ARG;
   return launched(dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
     return launch_bwd_pos(p, f, c, grad_sliced, skip, grad_positions);
+  }));
+}
+
+// The same with the caller's scratch for the level groups' slabs: the groups never meet in float atomics, so the same inputs
+// give the same bits on every call, ALSO while the stream is being captured into a graph (where the entry above has no scratch
+// and takes the atomic form) -- what a caller needs whose captured and eager results must agree bit for bit (box_trace.py).
+// The levels per thread are those of the entry above outside a capture (8 below 2^17 samples, else 2), hence so are the bits.
+// workspace_bytes below psdf_encode_backward_positions_workspace_bytes(): -1.
+constexpr int64_t POS_WS_LARGE_N = (int64_t)1 << 17;
+
+int64_t psdf_encode_backward_positions_workspace_bytes(int pos_dim, int nr_feat, int64_t N, int nr_levels, int concat_points) {
+  if (N <= 0 || nr_levels <= 0 || pos_dim <= 0 || nr_feat <= 0 || !concat_ok(concat_points)) return 0;
+  const int Lt = nr_levels + extra_levels(pos_dim, nr_feat, concat_points), lpb = N >= POS_WS_LARGE_N ? 2 : 8;
+  const int groups = (Lt + lpb - 1) / lpb;
+  return groups > 1 ? (int64_t)groups * N * pos_dim * (int64_t)sizeof(float) : 0;
+}
+
+int psdf_encode_backward_positions_masked_ws(int pos_dim, int nr_feat, int64_t N, int nr_levels, int capacity,
+                                             const float* positions, const float* lattice, const float* scale_factor,
+                                             const float* shifts, const float* window, int concat_points, float points_scaling,
+                                             const float* grad_sliced, const unsigned char* skip, float* grad_positions,
+                                             void* workspace, int64_t workspace_bytes, void* stream) {
+  EncCall c;
+  if (N == 0) return PSDF_OK;
+  if (!enc_call(c, pos_dim, nr_feat, N, nr_levels, capacity, positions, lattice, scale_factor, shifts, window, concat_points,
+                points_scaling, stream) || !grad_sliced || !grad_positions)
+    return PSDF_ERR_ARG;
+  const int64_t need = psdf_encode_backward_positions_workspace_bytes(pos_dim, nr_feat, N, nr_levels, concat_points);
+  if (need > 0 && (!workspace || workspace_bytes < need)) return PSDF_ERR_ARG;
+  return launched(dispatch_pf(pos_dim, nr_feat, [&](auto p, auto f) {
+    constexpr int P = decltype(p)::value, F = decltype(f)::value;
+    // (one group: a single thread adds to each entry, nothing to order, and no slab is used)
+    float* slabs = need > 0 ? (float*)workspace : nullptr;
+    if (N >= POS_WS_LARGE_N)
+      launch_bwd_pos_lpb<P, F, 2>(c, grad_sliced, skip, grad_positions, slabs == nullptr, slabs);
+    else
+      launch_bwd_pos_lpb<P, F, 8>(c, grad_sliced, skip, grad_positions, slabs == nullptr, slabs);
+    return PSDF_OK;
   }));
 }
 

@@ -219,7 +219,9 @@ class SdfFitNet(torch.nn.Module):
     scaled position appended (concat_points_scaling 1e-3), Linear(C, 32)-GELU-(32, 32)-GELU-(32, 32)-GELU-(32, 1 + geom_feat_size),
     leaky_relu_init, sdf_shift 1e-2 on the last bias.  Attribute names and methods are train_step.SdfNet's (`encoding`, `mlp_sdf`,
     `window(it)`, `sdf_only`, `sdf_and_gradient`): `MeshExtractor.from_sdf_net`, `SphereTracer(net.encoding, net.mlp_sdf, ...)` and
-    checkpoint.save(sdf=net) take a 3-D one as they are; a 4-D one is cut at a time with `time_slice`."""
+    checkpoint.save(sdf=net) take a 3-D one as they are; a 4-D one is cut at a time with `time_slice` for the mesh extractor, and
+    traced as it is, at a time, inside a box: `box_trace.BoxTracer(net.encoding, net.mlp_sdf, box)`, `render_box_traced`,
+    `BoxPlayer` (a 3-D one too, with no occupancy grid)."""
 
     def __init__(self, pos_dim=3, geom_feat_size=0, nr_iters_for_c2f=5000):
         super().__init__()
@@ -405,6 +407,23 @@ class SdfFitter:
         if self.pos_dim == 3:
             return MeshExtractor.from_sdf_net(self.net, self.iter)
         return MeshExtractor(self.net.time_slice(0.0 if t is None else t, self.iter), device=self.dev)
+
+    def box(self):
+        """the box the off-surface points are drawn from, as a box_trace.Box"""
+        from .box_trace import Box
+        lo, hi = self.box_lo[:3], self.box_hi[:3]
+        return Box([h - l for l, h in zip(lo, hi)], [(h + l) / 2 for l, h in zip(lo, hi)])
+
+    def tracer(self, box=None):
+        """a box_trace.BoxTracer over the fitted field inside `box` (default: the fit's own), with the current window"""
+        from .box_trace import BoxTracer
+        return BoxTracer(self.net.encoding, self.net.mlp_sdf, self.box() if box is None else box, self.net.window(self.iter))
+
+    def render(self, frame, t=None, box=None, **kw):
+        """-> box_trace.BoxTracedFrame: the fitted field as `frame` sees it (a 4-D one at time t); kw: render_box_traced's"""
+        from .box_trace import render_box_traced
+        kw.setdefault("it", self.iter)
+        return render_box_traced(self.net, self.box() if box is None else box, frame, time_val=t, **kw)
 
     # ---- checkpoints: the reference's sdf_model.pt (models.py:296-307) through checkpoint.py
     def save_checkpoint(self, folder):
