@@ -22,7 +22,6 @@ reference traces them from the camera centre; rays are independent, so every oth
 stay in their slots, masked out of the evaluations, instead of being compacted away with boolean masks each iteration; the end
 points are the compacting loop's bit for bit (tests/test_gpu_box_trace.py).  CPU tensors raise PsdfError: there is no CPU path.
 """
-import ctypes
 import dataclasses
 from typing import Optional
 
@@ -31,8 +30,7 @@ import torch
 
 from . import _lib as L
 from .bridge import OccupancyGrid
-from .encoding import _head, _tail, encode_forward_raw
-from .mlp import _dims_array, mlp_forward_raw, pack_params
+from .net_eval import masked_sdf, masked_sdf_gradient, one_row_head
 
 
 def _triple(v):
@@ -98,12 +96,9 @@ class BoxTracer:
 
     # ---- building blocks -----------------------------------------------------------------------------------
     def _sdf(self, pts, dims, packed, skip=None, out=None, feat_buf=None):
-        """SDF channel of the net at `pts` [N, P] -> (feat [C, N], sdf [1, N]), as SphereTracer._sdf: masked points are not
-        evaluated and keep their entries of `out`"""
-        e = self.enc
-        feat = encode_forward_raw(e.cfg, pts, e.lattice_values.detach(), e.scale_factor, e.random_shift_per_level.detach(),
-                                  self.window, skip=skip, out=feat_buf)
-        return feat, mlp_forward_raw(dims, feat, packed, skip=skip, out=out)
+        """SDF channel of the net at `pts` [N, P] -> (feat [C, N], sdf [1, N]): net_eval.masked_sdf (masked points are not
+        evaluated and keep their entries of `out`).  A method so that a test can put a field of its own in its place."""
+        return masked_sdf(self.enc, self.window, dims, packed, pts, skip=skip, out=out, feat_buf=feat_buf)
 
     def _check_time(self, time_val):
         if self.pos_dim == 4 and time_val is None:
@@ -121,12 +116,9 @@ class BoxTracer:
         L.call("psdf_box_trace_begin", L.c_i(R), L.c_i(P), box._min_c, box._max_c, L.ptr(o), L.ptr(d),
                L.ptr(self._time) if P == 4 else None, L.ptr(pts), L.ptr(conv), L.ptr(no_hit), L.stream())
         self.no_hit = no_hit
-        # channel 0 of the last layer is the SDF (models.py:190-192): a 1-row head, as SphereTracer
-        ws = [l.weight.detach() for l in self.mlp.layers]
-        bs = [l.bias.detach() for l in self.mlp.layers]
-        ws[-1], bs[-1] = ws[-1][0:1].contiguous(), bs[-1][0:1].contiguous()
-        dims = list(self.mlp.dims[:-1]) + [1]
-        packed = pack_params(dims, ws, bs)
+        # channel 0 of the last layer is the SDF (models.py:190-192): a 1-row head
+        head = one_row_head(self.mlp, pack=True)
+        dims, packed = head.dims, head.packed
         sdf = torch.zeros((1, R), dtype=torch.float32, device=dev)
         feat_buf = torch.zeros((self.enc.cfg.channels, R), dtype=torch.float32, device=dev)
         for _ in range(nr_sphere_traces):
@@ -139,26 +131,9 @@ class BoxTracer:
         # the masked MLP evaluates a partly masked 32-sample tile in full, and writes all of it: a ray that missed the box would
         # hold the net's value at zero features.  It was never evaluated and reports 0.
         sdf.masked_fill_(no_hit.view(1, -1), 0.0)
-        grads = None
-        if return_gradients:
-            # d sdf / d x = encode_backward_positions( mlp_backward_dX( 1 ) ); the level groups of the position backward meet in
-            # this call's scratch, in group order: the captured trace's normals are the eager trace's bit for bit
-            n_layers = len(dims) - 1
-            d_feat = torch.empty_like(feat)
-            gy = torch.ones_like(sdf)
-            Wp = (ctypes.c_void_p * n_layers)(*[w.data_ptr() for w in ws])
-            Bp = (ctypes.c_void_p * n_layers)(*[b.data_ptr() for b in bs])
-            L.call("psdf_mlp_backward_data_masked", L.c_i(n_layers), _dims_array(dims), L.c_l(R), L.ptr(feat), Wp, Bp, L.ptr(gy),
-                   L.ptr(no_hit), L.ptr(d_feat), L.stream())
-            grads = torch.zeros((R, P), dtype=torch.float32, device=dev)
-            cfg = self.enc.cfg
-            fn = L.lib().psdf_encode_backward_positions_workspace_bytes
-            fn.restype = ctypes.c_int64
-            nbytes = int(fn(L.c_i(cfg.pos_dim), L.c_i(cfg.nr_feat), L.c_l(R), L.c_i(cfg.nr_levels), L.c_i(int(cfg.concat_mode))))
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes > 0 else None
-            L.call("psdf_encode_backward_positions_masked_ws", *_head(cfg, R), L.ptr(pts), L.ptr(self.enc.lattice_values.detach()),
-                   L.ptr(self.enc.scale_factor), L.ptr(self.enc.random_shift_per_level.detach()), L.ptr(self.window), *_tail(cfg),
-                   L.ptr(d_feat), L.ptr(no_hit), L.ptr(grads), L.ptr(scratch), L.c_l(nbytes), L.stream())
+        # the level groups of the position backward meet in the call's scratch, in group order: the captured trace's normals are
+        # the eager trace's bit for bit
+        grads = masked_sdf_gradient(self.enc, self.window, head, pts, feat, no_hit, scratch=True) if return_gradients else None
         # rows of P floats, as the resolve kernel reads them
         self._rows = (pts, sdf, grads)
         return (pts if P == 3 else pts[:, :3], sdf.reshape(-1, 1), None if grads is None else (grads if P == 3 else grads[:, :3]),

@@ -351,6 +351,11 @@ class PermutoEncoding(torch.nn.Module):
                                       self.random_shift_per_level.detach(), anneal_window.contiguous())
 
 
+def map_range_val(v, in_lo, in_hi, out_lo, out_hi):
+    t = min(max((v - in_lo) / (in_hi - in_lo), 0.0), 1.0)
+    return out_lo + t * (out_hi - out_lo)
+
+
 class Coarse2Fine(torch.nn.Module):
     """Cosine-eased per-level window (same formula as reference common_utils.py:51-62)."""
 
@@ -380,6 +385,11 @@ class Coarse2Fine(torch.nn.Module):
     def window_readonly(self, t):
         """the cached window itself, no copy: for callers that promise not to modify it (train_step.SdfNet)"""
         return self._update(t)
+
+    def window_at(self, it, nr_iters, device):
+        """the window of training iteration `it` on `device`, read-only: t = map_range_val(it, 0, nr_iters, 0.3, 1.0), the
+        schedule of every net of the reference (models.py:186-187, :476-477)"""
+        return self.window_readonly(map_range_val(it, 0.0, nr_iters, 0.3, 1.0)).to(device)
 
     def get_last_t(self):
         return self.last_t

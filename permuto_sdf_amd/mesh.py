@@ -10,13 +10,13 @@ the level-major encode + MLP pair (1-row head, as the sphere tracer does), a sla
 of a slab are welded to those of its neighbours because their numbers come from one running prefix sum.  The result does not
 depend on the slab size, bit for bit.  With `occupancy_grid=` only the grid points next to an occupied voxel are evaluated.
 """
-import ctypes
 import os
 import warnings
 
 import torch
 
 from . import _lib as L
+from .net_eval import masked_sdf, masked_sdf_gradient, one_row_head
 
 _MSG_SHAPE = "Input volume should be a 3D numpy array with at least 2 samples per axis."
 _MSG_LEVEL = "Surface level must be within volume data range."
@@ -139,41 +139,23 @@ class MeshExtractor:
         return cls(net.encoding, net.mlp_sdf, net.window(iter_nr))
 
     # ---- the network: forward of a chunk, gradient at arbitrary points --------------------------------------------------
-    def _prepare_net(self):
-        from .mlp import pack_params
-        ws = [l.weight.detach() for l in self.mlp.layers]
-        bs = [l.bias.detach() for l in self.mlp.layers]
-        ws[-1], bs[-1] = ws[-1][0:1].contiguous(), bs[-1][0:1].contiguous()
-        dims = [l.weight.shape[1] for l in self.mlp.layers] + [1]
-        self._ws, self._bs, self._dims = [w.contiguous() for w in ws], [b.contiguous() for b in bs], dims
-        self._packed = pack_params(dims, self._ws, self._bs)
-
     def _forward(self, pts, skip, feat_flat, out):
         """out [1, N] <- SDF at pts [N,3]; points with skip != 0 keep what `out` holds"""
-        from .encoding import encode_forward_raw
-        from .mlp import mlp_forward_raw
-        e, N = self.enc, pts.shape[0]
-        feat = feat_flat[:e.cfg.channels * N].view(e.cfg.channels, N)
-        encode_forward_raw(e.cfg, pts, e.lattice_values.detach(), e.scale_factor, e.random_shift_per_level.detach(), self.window,
-                           skip=skip, out=feat)
-        mlp_forward_raw(self._dims, feat, self._packed, skip=skip, out=out)
+        C, N = self.enc.cfg.channels, pts.shape[0]
+        feat, _ = masked_sdf(self.enc, self.window, self._net.dims, self._net.packed, pts, skip=skip, out=out,
+                             feat_buf=feat_flat[:C * N].view(C, N))
         return feat
 
     @torch.no_grad()
     def sdf_gradient(self, pts, point_budget=None):
         """analytic d sdf / d x at pts [N,3] -> [N,3]: the sphere tracer's launches (masked MLP data gradient of a unit output
         gradient, then the encoding's position gradient), in chunks of `point_budget` points"""
-        from .encoding import _head, _tail
-        from .mlp import _dims_array
         if self.enc is None:
             raise L.PsdfError("MeshExtractor over a callable has no analytic gradient")
-        if not hasattr(self, "_packed"):
-            self._prepare_net()
+        if not hasattr(self, "_net"):
+            self._net = one_row_head(self.mlp, pack=True)
         B = int(point_budget or self.DEFAULT_POINT_BUDGET)
-        e, cfg, dev, dims = self.enc, self.enc.cfg, pts.device, self._dims
-        n_layers = len(dims) - 1
-        Wp = (ctypes.c_void_p * n_layers)(*[w.data_ptr() for w in self._ws])
-        Bp = (ctypes.c_void_p * n_layers)(*[b.data_ptr() for b in self._bs])
+        cfg, dev = self.enc.cfg, pts.device
         grads = torch.zeros((pts.shape[0], 3), dtype=torch.float32, device=dev)
         nb = min(B, max(1, pts.shape[0]))
         feat_flat = torch.empty(cfg.channels * nb, dtype=torch.float32, device=dev)
@@ -184,14 +166,8 @@ class MeshExtractor:
             N = p.shape[0]
             sdf = torch.zeros((1, N), dtype=torch.float32, device=dev)
             feat = self._forward(p, None, feat_flat, sdf)
-            d_feat = d_flat[:cfg.channels * N].view(cfg.channels, N)
-            gy = torch.ones_like(sdf)
-            g = grads[a:a + N]
-            L.call("psdf_mlp_backward_data_masked", L.c_i(n_layers), _dims_array(dims), L.c_l(N), L.ptr(feat), Wp, Bp, L.ptr(gy),
-                   L.ptr(live[:N]), L.ptr(d_feat), L.stream())
-            L.call("psdf_encode_backward_positions_masked", *_head(cfg, N), L.ptr(p), L.ptr(e.lattice_values.detach()),
-                   L.ptr(e.scale_factor), L.ptr(e.random_shift_per_level.detach()), L.ptr(self.window), *_tail(cfg), L.ptr(d_feat),
-                   L.ptr(live[:N]), L.ptr(g), L.stream())
+            masked_sdf_gradient(self.enc, self.window, self._net, p, feat, live[:N], out=grads[a:a + N],
+                                d_feat=d_flat[:cfg.channels * N].view(cfg.channels, N))
         return grads
 
     # ---- extraction ---------------------------------------------------------------------------------------------------
@@ -204,7 +180,7 @@ class MeshExtractor:
         dev = self.enc.lattice_values.device if self.enc is not None else (
             self.device or (occupancy_grid._dev if occupancy_grid is not None else torch.device("cuda", torch.cuda.current_device())))
         if self.enc is not None:
-            self._prepare_net()
+            self._net = one_row_head(self.mlp, pack=True)      # (every extraction: the net may have been trained on since)
         plane = n * n
         S = int(slab_planes) if slab_planes else max(1, self.DEFAULT_SLAB_POINTS // plane)
         S = max(1, min(S, n))

@@ -34,12 +34,13 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import parallel
 from .bridge import OccupancyGrid, PermutoSDF, RaySampler, Sphere, VolumeRendering, _per_sample
-from .encoding import Coarse2Fine, encode_forward_raw
+from .encoding import Coarse2Fine
 from .mlp import FusedMLP, _grad_views, mlp_backward_raw, mlp_forward_raw, mlp_forward_wide_f16_raw, pack_params
+from .net_eval import enc_backward, enc_forward, net_params, one_row_head, scalar_only, set_grads
 from .neus import (nerf_alpha, nerf_composite, nerf_composite_backward_raw, nerf_composite_forward_raw, sigmoid_rows_backward_raw,
                    sigmoid_rows_raw)
 from .optim import FusedAdamW
-from .train_step import BgNet, _Cumprod, _Integrate, _SumRay, _lattice, cat_fm, map_range_val
+from .train_step import BgNet, _Cumprod, _Integrate, _SumRay, _lattice, cat_fm
 
 PLAN_FIELDS = 4                    # PSDF_NERF_RENDER_PLAN_FIELDS of include/psdf.h
 FUSED_MAX_PER_RAY = 256
@@ -238,8 +239,7 @@ class NerfNet(BgNet):
         self.nr_iters_for_c2f = nr_iters_for_c2f
 
     def window(self, it):
-        t = map_range_val(it, 0.0, self.nr_iters_for_c2f, 0.3, 1.0)
-        return self.c2f.window_readonly(t).to(self.encoding.lattice_values.device)
+        return self.c2f.window_at(it, self.nr_iters_for_c2f, self.encoding.lattice_values.device)
 
     def forward(self, pos, dirs, it):
         """-> (colour [N, 3] after the sigmoid, RAW density [N, 1]: the softplus is the renderer's)"""
@@ -253,14 +253,9 @@ class NerfNet(BgNet):
     def get_only_density(self, points, it):
         """[N, 1]: softplus of the density alone (models.py:528-550), no graph: the lattice kernel and the density net with a
         1-row head"""
-        e = self.encoding
-        lin = list(self.mlp_feat_and_density.layers)
-        dims = [lin[0].in_features, 64, 64, 64, 1]
-        ws, bs = [l.weight.detach() for l in lin], [l.bias.detach() for l in lin]
-        ws[-1], bs[-1] = ws[-1][0:1].contiguous(), bs[-1][0:1].contiguous()
-        feat = encode_forward_raw(e.cfg, points.view(-1, self.pos_dim).contiguous(), e.lattice_values.detach(), e.scale_factor,
-                                  e.random_shift_per_level.detach(), self.window(it).contiguous())
-        return F.softplus(mlp_forward_raw(dims, feat, pack_params(dims, ws, bs)).view(-1, 1))
+        head = one_row_head(self.mlp_feat_and_density)      # (packed behind the lattice kernel)
+        raw = scalar_only(self.encoding, head, points.view(-1, self.pos_dim).contiguous(), self.window(it).contiguous())
+        return F.softplus(raw.view(-1, 1))
 
 
 class HyperParams:
@@ -369,15 +364,14 @@ class NerfTrainer:
     @staticmethod
     def _branch_forward(net, pts, dirs, it):
         """lattice -> density + feature net -> [gelu(features); SH4(dir)] (one launch) -> colour head -> sigmoid"""
-        from .train_manual import _enc_fwd, _net
         win = net.window(it).contiguous()
-        feat = _enc_fwd(net.encoding, pts, win)
-        net1 = d1, _, w1, b1 = _net(net.mlp_feat_and_density)
+        feat = enc_forward(net.encoding, pts, win)
+        net1 = d1, _, w1, b1 = net_params(net.mlp_feat_and_density)
         fd = mlp_forward_wide_f16_raw(d1, feat, w1, b1)                      # [65, M] on the fp16 matrix pipe
         if fd is None:      # (the library declined: fp32 MFMAs)
             fd = mlp_forward_raw(d1, feat, pack_params(d1, w1, b1))
         x2 = nerf_head_join_raw(fd, PermutoSDF.spherical_harmonics(dirs, 4))  # [80, M]
-        net2 = d2, _, w2, b2 = _net(net.mlp_rgb)
+        net2 = d2, _, w2, b2 = net_params(net.mlp_rgb)
         rgb = sigmoid_rows_raw(mlp_forward_raw(d2, x2, pack_params(d2, w2, b2)))   # [M, 3]
         return SimpleNamespace(net=net, pts=pts, win=win, feat=feat, fd=fd, x2=x2, net1=net1, net2=net2, rgb=rgb, raw_den=fd[0])
 
@@ -385,14 +379,13 @@ class NerfTrainer:
     def _branch_backward(B, g_raw, g_rgb, into1, into2):
         """the net's gradients into the zero-filled views into1 (density + feature net) / into2 (colour head), the lattice's
         into its touched-rows buffer"""
-        from .train_manual import _enc_bwd, _set_grads
         (d1, l1, w1, b1), (d2, l2, w2, b2) = B.net1, B.net2
         dX2, dW2, db2 = mlp_backward_raw(d2, B.x2, w2, b2, sigmoid_rows_backward_raw(g_rgb, B.rgb), need_dx=True, into=into2)
-        _set_grads(l2, dW2, db2)
+        set_grads(l2, dW2, db2)
         g_fd = nerf_head_join_backward_raw(g_raw, dX2, B.fd)                  # [65, M]
         dX, dW1, db1 = mlp_backward_raw(d1, B.feat, w1, b1, g_fd, need_dx=True, into=into1)
-        _set_grads(l1, dW1, db1)
-        _enc_bwd(B.net.encoding, B.pts, B.win, dX)
+        set_grads(l1, dW1, db1)
+        enc_backward(B.net.encoding, B.pts, B.win, dX)
 
     # ---- the two forms of a step
     @torch.no_grad()

@@ -22,8 +22,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .encoding import Coarse2Fine, PermutoEncoding, encode_forward_raw
+from .encoding import Coarse2Fine, PermutoEncoding
 from .mlp import FusedMLP, mlp_backward_raw, mlp_forward_raw, pack_params
+from .net_eval import enc_forward, net_params, one_row_head, scalar_only, sdf_gradient, sdf_gradient_backward
 from .optim import FusedAdamW
 
 PLAN_FIELDS = 4                              # PSDF_SDF_FIT_PLAN_FIELDS of include/psdf.h
@@ -209,11 +210,6 @@ def sdf_fit_loss_torch(sdf, gradients, normals, n_surf, weights=REFERENCE_WEIGHT
 
 
 # ---------------------------------------------------------------------------------------------------------------- the network
-def _map_range_val(v, in_lo, in_hi, out_lo, out_hi):
-    t = min(max((v - in_lo) / (in_hi - in_lo), 0.0), 1.0)
-    return out_lo + t * (out_hi - out_lo)
-
-
 class SdfFitNet(torch.nn.Module):
     """models.py:131-251 for in_channels = pos_dim: a 24-level lattice of capacity 2^18 over `pos_dim` dimensions with the
     scaled position appended (concat_points_scaling 1e-3), Linear(C, 32)-GELU-(32, 32)-GELU-(32, 32)-GELU-(32, 1 + geom_feat_size),
@@ -237,7 +233,7 @@ class SdfFitNet(torch.nn.Module):
         self.nr_iters_for_c2f = nr_iters_for_c2f
 
     def window(self, it):
-        return self.c2f.window_readonly(_map_range_val(it, 0.0, self.nr_iters_for_c2f, 0.3, 1.0)).to(self.encoding.lattice_values.device)
+        return self.c2f.window_at(it, self.nr_iters_for_c2f, self.encoding.lattice_values.device)
 
     def forward(self, points, it):
         """-> (sdf [N, 1], geometry features [N, geom_feat_size] or None)"""
@@ -246,21 +242,11 @@ class SdfFitNet(torch.nn.Module):
             return y, None
         return y[:, 0:1], y[:, 1:]
 
-    def _head_params(self):
-        lin = list(self.mlp_sdf.layers)
-        dims = [lin[0].in_features, 32, 32, 32, 1]
-        ws, bs = [l.weight.detach() for l in lin], [l.bias.detach() for l in lin]
-        ws[-1], bs[-1] = ws[-1][0:1].contiguous(), bs[-1][0:1].contiguous()
-        return dims, pack_params(dims, ws, bs)
-
     @torch.no_grad()
     def sdf_only(self, points, it, key=None):
         """[N, 1]: the SDF alone (row 0 of the last layer), no graph: the lattice kernel and the MLP with a 1-row head"""
-        e = self.encoding
-        dims, packed = self._head_params()
-        feat = encode_forward_raw(e.cfg, points.contiguous(), e.lattice_values.detach(), e.scale_factor,
-                                  e.random_shift_per_level.detach(), self.window(it).contiguous())
-        return mlp_forward_raw(dims, feat, packed).view(-1, 1)
+        head = one_row_head(self.mlp_sdf, pack=True)
+        return scalar_only(self.encoding, head, points.contiguous(), self.window(it).contiguous()).view(-1, 1)
 
     def sdf_and_gradient(self, points, it):  # models.py:236-251
         """-> (sdf [N, 1], d sdf / d points [N, pos_dim] with its graph, geometry features or None)"""
@@ -347,13 +333,12 @@ class SdfFitter:
     # ---- the two forms of a step
     @torch.no_grad()
     def _step_hand_written(self, idx, u, it):
-        from .train_manual import _enc_fwd, _net, sdf_gradient, sdf_gradient_backward
         net_m, enc, mlp = self.net, self.net.encoding, self.net.mlp_sdf
         points, normals = sdf_fit_batch_raw(self.cloud, idx, u, self.box_lo, self.box_hi)
-        dims, _, ws, bs = _net(mlp)
+        dims, _, ws, bs = net_params(mlp)
         net = SimpleNamespace(dims=dims, ws=ws, bs=bs, win=net_m.window(it).contiguous(), packed=pack_params(dims, ws, bs),
                               gb=self.grad_buffer)
-        feat = _enc_fwd(enc, points, net.win)
+        feat = enc_forward(enc, points, net.win)
         y = mlp_forward_raw(dims, feat, net.packed)                                        # [1 + geom, N]; row 0: the SDF
         n, dfeat, e0 = sdf_gradient(enc, feat, points, net, torch.zeros_like(points))
         self.last_terms = torch.empty(4, dtype=torch.float32, device=self.dev)

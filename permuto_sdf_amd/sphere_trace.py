@@ -8,13 +8,10 @@ replayed per frame (``SphereTracer.capture``).  Converged rays are masked out of
 converged 32-ray tiles no MLP), rays that met no occupied voxel also out of the final evaluation.  End points are bit
 identical to the reference-style compacting loop (tests/test_gpu_sphere_trace.py).
 """
-import ctypes
-
 import torch
 
 from . import _lib as L
-from .encoding import _head, _tail, encode_forward_raw
-from .mlp import _dims_array, mlp_forward_raw, pack_params
+from .net_eval import masked_sdf, masked_sdf_gradient, one_row_head
 
 
 class SphereTracer:
@@ -30,14 +27,9 @@ class SphereTracer:
 
     # ---- building blocks -----------------------------------------------------------------------------------
     def _sdf(self, pts, dims, packed, skip=None, out=None, feat_buf=None):
-        """SDF channel of the net at `pts` -> (feat [C,N], sdf [1,N]).  Two launches: the level-major encode kernel keeps
-        one 2-MiB table at a time in every XCD's L2 and runs at full occupancy, which beats the single fused launch
-        (csrc/fused.hip, whose 24 tables thrash the L2) even more clearly at 24 levels; both honour the per-ray mask
-        (converged rays: no gathers, fully converged 32-ray tiles: no MLP)."""
-        e = self.enc
-        feat = encode_forward_raw(e.cfg, pts, e.lattice_values.detach(), e.scale_factor,
-                                  e.random_shift_per_level.detach(), self.window, skip=skip, out=feat_buf)
-        return feat, mlp_forward_raw(dims, feat, packed, skip=skip, out=out)
+        """SDF channel of the net at `pts` -> (feat [C,N], sdf [1,N]): net_eval.masked_sdf (converged rays: no gathers, fully
+        converged 32-ray tiles: no MLP).  A method so that a test can put a field of its own in its place."""
+        return masked_sdf(self.enc, self.window, dims, packed, pts, skip=skip, out=out, feat_buf=feat_buf)
 
     def _grid_args(self):
         g = self.grid
@@ -65,11 +57,8 @@ class SphereTracer:
         self.no_hit = no_hit
         # channel 0 of the last layer is the SDF (models.py:190-192); the geometry features are not needed to trace,
         # so the net is evaluated with a 1-row head (same arithmetic for that row, 1/33 of the output traffic)
-        ws = [l.weight.detach() for l in self.mlp.layers]
-        bs = [l.bias.detach() for l in self.mlp.layers]
-        ws[-1], bs[-1] = ws[-1][0:1].contiguous(), bs[-1][0:1].contiguous()
-        dims = list(self.mlp.dims[:-1]) + [1]
-        packed = pack_params(dims, ws, bs)
+        head = one_row_head(self.mlp, pack=True)
+        dims, packed = head.dims, head.packed
         sdf = torch.zeros((1, R), dtype=torch.float32, device=dev)
         feat_buf = torch.zeros((self.enc.cfg.channels, R), dtype=torch.float32, device=dev)
         if self.compact_marches:   # work buffers of the two-launch step: flags, list, one counter per iteration (one fill)
@@ -91,21 +80,8 @@ class SphereTracer:
         # final SDF (+ analytic normal) at the end points of the rays that took part
         sdf.zero_()
         feat, sdf = self._sdf(pts, dims, packed, skip=no_hit, out=sdf, feat_buf=feat_buf)
-        grads = None
-        if return_gradients:
-            # analytic normal: d sdf / d x = encode_backward_positions( mlp_backward_dX( 1 ) )
-            n_layers = len(dims) - 1
-            d_feat = torch.empty_like(feat)
-            gy = torch.ones_like(sdf)
-            Wp = (ctypes.c_void_p * n_layers)(*[w.data_ptr() for w in ws])
-            Bp = (ctypes.c_void_p * n_layers)(*[b.data_ptr() for b in bs])
-            L.call("psdf_mlp_backward_data_masked", L.c_i(n_layers), _dims_array(dims), L.c_l(R), L.ptr(feat), Wp, Bp,
-                   L.ptr(gy), L.ptr(no_hit), L.ptr(d_feat), L.stream())
-            grads = torch.zeros((R, 3), dtype=torch.float32, device=dev)
-            cfg = self.enc.cfg
-            L.call("psdf_encode_backward_positions_masked", *_head(cfg, R), L.ptr(pts), L.ptr(self.enc.lattice_values.detach()),
-                   L.ptr(self.enc.scale_factor), L.ptr(self.enc.random_shift_per_level.detach()), L.ptr(self.window),
-                   *_tail(cfg), L.ptr(d_feat), L.ptr(no_hit), L.ptr(grads), L.stream())
+        # the analytic normal of the rays that took part
+        grads = masked_sdf_gradient(self.enc, self.window, head, pts, feat, no_hit) if return_gradients else None
         return pts, sdf.reshape(-1, 1), grads, conv
 
     # ---- hipGraph ------------------------------------------------------------------------------------------------

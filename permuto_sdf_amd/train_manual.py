@@ -28,98 +28,19 @@ import torch
 
 from . import _lib as L
 from .bridge import PermutoSDF, RaySamplesPacked, VolumeRendering as VR
-from .encoding import encode_backward_raw, encode_double_backward_raw, encode_forward_raw
+from .encoding import map_range_val
 from .mlp import (_grad_views, double_backward_plus_supported, mlp_forward_wide_f16_raw, lipshitz_normalize_all_backward_raw, lipshitz_normalize_all_raw, mlp_backward_raw,
-                  mlp_double_backward, mlp_forward_raw, pack_params)
+                  mlp_forward_raw, pack_params)
+from .net_eval import enc_backward, enc_forward, net_params, sdf_gradient, sdf_gradient_backward, set_grads
 from .neus import (eikonal_loss_raw, l1_loss_raw, nerf_composite_backward_raw, nerf_composite_forward_raw, neus_composite_backward_raw,
                    neus_composite_forward_raw, sigmoid_rows_backward_raw, sigmoid_rows_raw)
-from .train_step import Trainer, map_range_val
-
-
-def _raw(enc):
-    """(cfg, lattice, scale factors, shifts, touched-rows record) of an encoding as the raw kernels take them.  Kept on the module:
-    a step asks 17 times, and every ask is five nn.Module attribute lookups and two detach() calls on the host -- the step is host
-    bound at iteration 0 (tools/prof_step.py).  Rebuilt when the parameter's storage has moved (.to(), load of a new tensor) or the
-    touched-rows record was replaced."""
-    lat = enc._parameters["lattice_values"]
-    r = enc.__dict__.get("_psdf_raw")
-    if r is None or r[5] != lat.data_ptr() or r[4] is not enc.__dict__.get("touched_rows"):
-        r = (enc.cfg, lat.detach(), enc.scale_factor, enc.random_shift_per_level.detach(), enc.touched_rows, lat.data_ptr())
-        enc.__dict__["_psdf_raw"] = r
-    return r
-
-
-def _enc_fwd(enc, pts, win, train=True, out=None):
-    cfg, lat, sf, sh, tr, _ = _raw(enc)
-    return encode_forward_raw(cfg, pts, lat, sf, sh, win, out=out, touched=tr.touched if train else None,
-                              block_rows_log2=tr.block_rows_log2)
-
-
-def _enc_bwd(enc, pts, win, g_fm, want_pos=False, want_lattice=True, zeroed=None):
-    """lattice gradient into the encoding's persistent buffer; optionally the position gradient [N, P] (the kernels accumulate:
-    `zeroed` = a zero-filled [N, P] tensor to use for it, else one is filled here)"""
-    g_pos = (zeroed if zeroed is not None else torch.zeros_like(pts)) if want_pos else None
-    cfg, lat, sf, sh, tr, _ = _raw(enc)
-    encode_backward_raw(cfg, pts, lat, sf, sh, win, g_fm, tr.grad if want_lattice else None, g_pos)
-    return g_pos
-
-
-def _enc_dbl_gather(enc, pts, win, dd_pos, g_fm):
-    """backward of the position gradient, first half: the gradient w.r.t. the feature gradient [C, N] (a gather)"""
-    gg = torch.empty_like(g_fm)
-    cfg, lat, sf, sh, _, _ = _raw(enc)
-    encode_double_backward_raw(cfg, pts, lat, sf, sh, win, dd_pos, g_fm, None, gg)
-    return gg
-
-
-def _enc_dbl_scatter(enc, pts, win, dd_pos, g_fm, direct_fm):
-    """second half, together with the plain backward of `direct_fm` (the gradient that reached the features): ONE scatter of both
-    into the lattice buffer -- they land on the same rows of the same simplices"""
-    cfg, lat, sf, sh, tr, _ = _raw(enc)
-    encode_double_backward_raw(cfg, pts, lat, sf, sh, win, dd_pos, g_fm, tr.grad, None, direct_fm)
+from .train_step import Trainer
 
 
 def _normalize3(x, gy=None):
     out = torch.empty_like(x)
     L.call("psdf_normalize3", L.c_l(x.shape[0]), L.ptr(x), L.ptr(gy), L.ptr(out), L.stream())
     return out
-
-
-def _set_grads(layers, dWs, dbs):
-    for l, dW, db in zip(layers, dWs, dbs):
-        l.weight.grad, l.bias.grad = dW, db
-
-
-def _net(mlp):
-    """(dims, layers, weights, biases) of an MLP module as the raw kernels take them"""
-    layers = list(mlp.layers)
-    return mlp.dims, layers, [l.weight for l in layers], [l.bias for l in layers]
-
-
-def sdf_gradient(enc, feat, pts, net, zeroed=None):
-    """n = d sdf / d p and the feature gradient it came through, for the SDF network (encoding `enc`, MLP `net`: a record with
-    dims, ws, bs, win) evaluated at pts with features feat -> (n [N, P], dfeat [C, N], e0).  zeroed: a zero-filled [N, P] tensor
-    for n (one is filled here otherwise)"""
-    e0 = None       # "the unit gradient of output 0": the kernels take NULL for it (no [33, N] tensor that is 1 in one row)
-    dfeat, _, _ = mlp_backward_raw(net.dims, feat, net.ws, net.bs, e0, need_dx=True, need_dw=False)
-    n = _enc_bwd(enc, pts, net.win, dfeat, want_pos=True, want_lattice=False, zeroed=zeroed)
-    return n, dfeat, e0
-
-
-def sdf_gradient_backward(enc, mlp_module, g_n, feat, dfeat, e0, pts, net, extra_dfeat=None, extra_gy=None, zeroed=None):
-    """backward of  n = d sdf / d p  for an upstream g_n [N, P]: lattice and parameter gradients are accumulated (into the
-    encoding's touched-rows buffer and net.gb); returns the position gradient when `zeroed`, a zero-filled [N, P] tensor for it,
-    is given (the shifted points of the curvature term depend on n).  extra_gy [33, N]: an upstream gradient of the net's outputs
-    on the same samples -- its plain backward rides in the double backward's launch (round 6: one forward recomputation and one
-    sweep for both); extra_dfeat: a data gradient to add instead (the two-launch form)"""
-    win = net.win
-    gg = _enc_dbl_gather(enc, pts, win, g_n, dfeat)
-    dX2, _, _ = mlp_double_backward(net.dims, feat, net.ws, net.bs, e0, gg, into=(net.gb.dWs, net.gb.dbs), module=mlp_module,
-                                    gy2_fm=extra_gy)
-    if extra_dfeat is not None:
-        dX2 = dX2 + extra_dfeat
-    _enc_dbl_scatter(enc, pts, win, g_n, dfeat, dX2)
-    return _enc_bwd(enc, pts, win, dX2, want_pos=True, want_lattice=False, zeroed=zeroed) if zeroed is not None else None
 
 
 class _Step:
@@ -275,19 +196,19 @@ class ManualTrainer(Trainer):
     # ------------------------------------------------------------------ the background branch (NerfHash, models.py:431-526)
     def _bg_forward(self, bg, calib):
         """4-D lattice -> density + feature net -> [gelu(features), SH4(dir)] -> colour head -> (calibrated) sigmoid.  Everything
-        the compositing and the backward need, as a record (net1, net2: `_net` of the two MLPs; rgbb_raw, ridx: None without calibration)."""
+        the compositing and the backward need, as a record (net1, net2: `net_params` of the two MLPs; rgbb_raw, ridx: None without calibration)."""
         bgn = self.bg
         self._params_ready(2)              # the background lattice's parameters (all-gather of the previous step, data parallel)
         p4, dirs_b = bg.samples_pos_4d, bg.samples_dirs
-        feat4 = _enc_fwd(bgn.encoding, p4, bgn._win)
-        net1 = d1, _, w1b, b1b = _net(bgn.mlp_feat_and_density)
+        feat4 = enc_forward(bgn.encoding, p4, bgn._win)
+        net1 = d1, _, w1b, b1b = net_params(bgn.mlp_feat_and_density)
         fd = mlp_forward_wide_f16_raw(d1, feat4, w1b, b1b)                                # [65, M] on the fp16 matrix pipe (round 6)
         if fd is None:      # (the library declined: fp32 MFMAs)
             fd = mlp_forward_raw(d1, feat4, pack_params(d1, w1b, b1b))
         gel = torch.nn.functional.gelu(fd[1:65])
         sh4 = PermutoSDF.spherical_harmonics(dirs_b, 4)
         x2 = torch.cat([gel, sh4.t()], 0)                                                 # [80, M]
-        net2 = d2, _, w2b, b2b = _net(bgn.mlp_rgb)
+        net2 = d2, _, w2b, b2b = net_params(bgn.mlp_rgb)
         rgbb_fm = mlp_forward_raw(d2, x2, pack_params(d2, w2b, b2b))                      # [3, M]
         rgbb, rgbb_raw, ridx = _calib_sigmoid(calib, rgbb_fm, bg.ray_start_end_idx)
         return SimpleNamespace(p4=p4, feat4=feat4, fd=fd, x2=x2, net1=net1, net2=net2, rgbb=rgbb, rgbb_raw=rgbb_raw, ridx=ridx,
@@ -299,11 +220,11 @@ class ManualTrainer(Trainer):
         bgn, (d1, l1b, w1b, b1b), (d2, l2b, w2b, b2b) = self.bg, B.net1, B.net2
         g_pre_b_fm, g_cw, g_cb = _calib_sigmoid_backward(calib, g_rgbb, B.rgbb, B.rgbb_raw, B.ridx)
         dX2b, dW2b, db2b = mlp_backward_raw(d2, B.x2, w2b, b2b, g_pre_b_fm, need_dx=True, into=into2)
-        _set_grads(l2b, dW2b, db2b)
+        set_grads(l2b, dW2b, db2b)
         g_fd = torch.cat([g_raw.view(1, -1), torch.ops.aten.gelu_backward(dX2b[:64], B.fd[1:65])], 0)      # [65, M]
         dX4, dW1b, db1b = mlp_backward_raw(d1, B.feat4, w1b, b1b, g_fd, need_dx=True, into=into1)
-        _set_grads(l1b, dW1b, db1b)
-        _enc_bwd(bgn.encoding, B.p4, bgn._win, dX4)
+        set_grads(l1b, dW1b, db1b)
+        enc_backward(bgn.encoding, B.p4, bgn._win, dX4)
         return g_cw, g_cb
 
     # ------------------------------------------------------------------ per-ray colour calibration (the sigmoids: _calib_sigmoid*)
@@ -335,11 +256,11 @@ class ManualTrainer(Trainer):
         x_rgb = [colour encoding | SH | normal | geometry features]; rgb_raw, ridx: None without calibration)"""
         net, rgbn = st.net, self.rgb
         pts = fgs.samples_pos
-        feat = _enc_fwd(self.sdf.encoding, pts, net.win)
+        feat = enc_forward(self.sdf.encoding, pts, net.win)
         y = mlp_forward_raw(net.dims, feat, net.packed)                                   # [33, N]: sdf, geometry features
         n, dfeat, e0 = self._sdf_gradient(feat, pts, net)
         self._params_ready(1)              # the colour lattice's parameters: before the colour encode, not earlier
-        feat2 = _enc_fwd(rgbn.encoding, pts, rgbn._win)
+        feat2 = enc_forward(rgbn.encoding, pts, rgbn._win)
         sh = PermutoSDF.spherical_harmonics(fgs.samples_dirs, 5)
         nn = _normalize3(n)
         x_rgb = torch.cat([feat2, sh.t(), nn.t(), y[1:]], 0)                              # [111, N]
@@ -367,7 +288,7 @@ class ManualTrainer(Trainer):
         dws, dcs = lipshitz_normalize_all_backward_raw(m.weights_per_layer, m.lipshitz_bound_per_layer, dWn, dc_flat=st.arena[3])
         for i, (w, c) in enumerate(zip(m.weights_per_layer, m.lipshitz_bound_per_layer)):
             w.grad, c.grad, m.biases_per_layer[i].grad = dws[i], dcs[i].view_as(c), dbr[i]
-        _enc_bwd(rgbn.encoding, fg.pts, rgbn._win, dXr[:fg.c_enc])
+        enc_backward(rgbn.encoding, fg.pts, rgbn._win, dXr[:fg.c_enc])
         self._dp_lattice_final(1)          # right after the colour encode backward: the colour lattice's gradient is final
         g_n = st.g_n + g_nc + _normalize3(fg.n, dXr[fg.c_sh:fg.c_sh + 3].t().contiguous())
         g_y = torch.cat([g_sdf.view(1, -1), dXr[fg.c_sh + 3:]], 0)                        # [33, N]
@@ -388,7 +309,7 @@ class ManualTrainer(Trainer):
         rnd = torch.randn_like(fg.pts)     # torch's first random draw of the step after the rays
         shifted = torch.empty_like(fg.pts)
         L.call("psdf_curvature_shift", L.c_l(n_fg), L.ptr(fg.pts), L.ptr(fg.n), L.ptr(rnd), L.c_f(1e-4), None, L.ptr(shifted), L.stream())
-        feat_s = _enc_fwd(self.sdf.encoding, shifted, net.win)
+        feat_s = enc_forward(self.sdf.encoding, shifted, net.win)
         n2, dfeat_s, _ = self._sdf_gradient(feat_s, shifted, net)
         ga, gb2 = torch.empty_like(fg.n), torch.empty_like(n2)
         L.call("psdf_curvature_loss", L.c_l(n_fg), L.ptr(fg.n), L.ptr(n2), L.c_f(weight / n_fg), L.ptr(st.loss), L.ptr(ga), L.ptr(gb2),
@@ -409,7 +330,7 @@ class ManualTrainer(Trainer):
     def _offsurface_forward(self, st):
         net = st.net
         st.off = self.sphere.rand_points_inside(1024)      # torch's random draw after the curvature shift's
-        st.feat_o = _enc_fwd(self.sdf.encoding, st.off, net.win)
+        st.feat_o = enc_forward(self.sdf.encoding, st.off, net.win)
         y_o = mlp_forward_raw(net.dims, st.feat_o, net.packed)
         # the term's gradient w.r.t. the net's 33 outputs is zero except in row 0 (the SDF): a persistent [33, 1024] buffer whose
         # rows 1.. stay zero, row 0 rewritten by the loss kernel every step (no fill, no copy)
@@ -421,7 +342,7 @@ class ManualTrainer(Trainer):
     def _offsurface_backward(self, st):
         net = st.net
         dXo, _, _ = mlp_backward_raw(net.dims, st.feat_o, net.ws, net.bs, self._g_yo, need_dx=True, into=(net.gb.dWs, net.gb.dbs))
-        _enc_bwd(self.sdf.encoding, st.off, net.win, dXo)
+        enc_backward(self.sdf.encoding, st.off, net.win, dXo)
 
     # ------------------------------------------------------------------ one iteration of the main phase
     def _main_phase(self, reel, it, git, eikonal_weight):
@@ -460,7 +381,7 @@ class ManualTrainer(Trainer):
             st.bg = self._bg_forward(bgs, st.calib)
         st.n_fg = fgs.samples_pos.shape[0]
         self._params_ready(0)              # the SDF lattice's parameters, before anything below reads them (data parallel)
-        dims, _, ws, bs = _net(sdfn.mlp_sdf)
+        dims, _, ws, bs = net_params(sdfn.mlp_sdf)
         # the SDF network as the step's three evaluations share it; win: this iteration's lattice window, gb: its gradient buffer
         st.net = SimpleNamespace(dims=dims, ws=ws, bs=bs, win=sdfn.window(it).contiguous(), packed=pack_params(dims, ws, bs),
                                  gb=self.grad_buffers[0])

@@ -38,9 +38,10 @@ import torch.nn.functional as F
 
 from . import parallel
 from .bridge import OccupancyGrid, PermutoSDF, RaySampler, Sphere, VolumeRendering
-from .encoding import Coarse2Fine, PermutoEncoding
+from .encoding import Coarse2Fine, PermutoEncoding, map_range_val  # noqa: F401  (map_range_val: importable from here as ever)
 from .fused import encode_mlp_forward_raw
-from .mlp import FusedMLP, LipshitzMLP, pack_params
+from .mlp import FusedMLP, LipshitzMLP
+from .net_eval import one_row_head
 from .neus import (curvature_loss, curvature_shift, eikonal_loss, l1_loss, nerf_alpha, nerf_composite, neus_alpha, neus_composite,
                    normalize3, offsurface_loss)
 from .optim import FusedAdamW
@@ -93,11 +94,6 @@ def lr_schedule(global_iter, hp):
         return hp.lr * (float(k) / W)
     m = k - (W + 1)
     return hp.lr * hp.lr_gamma ** sum(1 for ms in hp.lr_milestones if ms <= m)
-
-
-def map_range_val(v, in_lo, in_hi, out_lo, out_hi):
-    t = min(max((v - in_lo) / (in_hi - in_lo), 0.0), 1.0)
-    return out_lo + t * (out_hi - out_lo)
 
 
 # ------------------------------------------------------------------------------------- differentiable compositing
@@ -198,7 +194,7 @@ class SdfNet(torch.nn.Module):
 
     def window(self, it):
         # read-only use: the cached window itself (no copy per call; Coarse2Fine.__call__ hands out copies)
-        return self.c2f.window_readonly(map_range_val(it, 0.0, self.nr_iters_for_c2f, 0.3, 1.0)).to(self.encoding.lattice_values.device)
+        return self.c2f.window_at(it, self.nr_iters_for_c2f, self.encoding.lattice_values.device)
 
     def forward(self, points, it):
         return _SplitHead.apply(self.mlp_sdf(self.encoding(points, self.window(it))))
@@ -208,18 +204,15 @@ class SdfNet(torch.nn.Module):
         """[N,1]; the SDF is row 0 of the last layer (models.py:190).  `key`: anything that changes whenever the parameters do
         (the trainer passes its iteration counter): calls with the same key share one packed weight image instead of packing
         it again (three evaluations per training step)."""
-        lin = list(self.mlp_sdf.layers)
-        dims = [lin[0].in_features, 32, 32, 32, 1]
         if key is not None:      # torch-level writes (load_state_dict, copy_) bump _version; the fused optimiser's do not: hence both
-            key = (key, tuple(p._version for l in lin for p in (l.weight, l.bias)))
+            key = (key, tuple(p._version for l in self.mlp_sdf.layers for p in (l.weight, l.bias)))
         cached = getattr(self, "_sdf_only_packed", None)
         if key is not None and cached is not None and cached[0] == key:
-            packed = cached[1]
+            _, dims, packed = cached
         else:
-            ws, bs = [l.weight for l in lin], [l.bias for l in lin]
-            ws[-1], bs[-1] = ws[-1][0:1].contiguous(), bs[-1][0:1].contiguous()
-            packed = pack_params(dims, ws, bs)
-            self._sdf_only_packed = (key, packed) if key is not None else None
+            head = one_row_head(self.mlp_sdf, pack=True)
+            dims, packed = head.dims, head.packed
+            self._sdf_only_packed = (key, dims, packed) if key is not None else None
         e = self.encoding
         y, _ = encode_mlp_forward_raw(e.cfg, points.contiguous(), e.lattice_values.detach(), e.scale_factor,
                                       e.random_shift_per_level.detach(), self.window(it).contiguous(), dims, packed)

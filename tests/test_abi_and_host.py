@@ -285,10 +285,10 @@ def test_binned_backward_plan_refuses_what_its_32_bit_offsets_cannot_address(lib
 
 
 def test_cached_raw_views_of_an_encoding_follow_the_parameter():
-    """train_manual._raw caches (cfg, detached lattice, scale factors, shifts, touched-rows record) on the module (the hand-written
+    """net_eval.raw caches (cfg, detached lattice, scale factors, shifts, touched-rows record) on the module (the hand-written
     step asks 17 times per iteration); the cache must notice a lattice whose storage moved and a replaced touched-rows record"""
     from permuto_sdf_amd.encoding import PermutoEncoding
-    from permuto_sdf_amd.train_manual import _raw
+    from permuto_sdf_amd.net_eval import raw as _raw
     enc = PermutoEncoding(3, 256, 4, 2, [1.0, 2.0, 4.0, 8.0])
     tr0 = enc.enable_touched_rows()
     r0 = _raw(enc)
