@@ -148,6 +148,37 @@ int psdf_nerf_composite_backward(int nr_rays, const int* start_end, int equal, i
                                  const float* rgb, int reference_compat, float* grad_raw_density, float* grad_rgb,
                                  float* grad_fg_bg, void* stream);
 
+/* ---- neus_render.hip ---- */
+/* The NeuS render of a `--with_mask` training step (train_permuto_sdf.py:153-154,381-383): psdf_neus_composite_forward with the
+   per-ray weight sum as a third output, its backward with a gradient into it, and the step's colour + mask loss in one call. */
+/* host only: the launch plan (csrc/neus_render_plan.h) -> out [PSDF_NEUS_RENDER_PLAN_FIELDS] int64: 0 the register chunks K of
+   the ray backward for max_per_ray (1, 2, 4); 1 workgroups of the loss kernel for nr_rays; 2 bytes of the workspace
+   psdf_neus_mask_loss needs for nr_rays (0 up to the single-group limit); 3 that limit (8192 rays).
+   -1: nr_rays < 0, max_per_ray < 1; -2: nr_rays > (2^31 - 1) / 3, max_per_ray > 256 */
+#define PSDF_NEUS_RENDER_PLAN_FIELDS 4
+int psdf_neus_render_plan(int64_t nr_rays, int max_per_ray, int64_t* out);
+/* one launch, any ray length: pred [R,3], weights_sum [R] = sum alpha T, bg_transmittance [R]; each may be NULL (one at least is
+   given; rgb may be NULL without pred).  Empty and overflowed rays: 0, 0, 1.  pred and bg_transmittance have the bits of
+   psdf_neus_composite_forward. */
+int psdf_neus_render_forward(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, const float* sdf,
+    const float* dirs, const float* gradients, const float* dt, const float* rgb, const float* inv_s, float cos_anneal_ratio,
+    float* pred, float* weights_sum, float* bg_transmittance, void* stream);
+/* its backward in one launch for grad_pred [R,3], grad_weights_sum [R], grad_bg_transmittance [R] (each may be NULL, one at
+   least is given) -> grad_sdf [N]; optional grad_gradients [N,3], grad_rgb [N,3], grad_inv_s [1] (accumulated into).
+   max_per_ray, reference_compat, skipped rays: as psdf_neus_composite_backward, whose bits every output has when
+   grad_weights_sum is NULL.  A ray longer than max_per_ray rounded up to 64 K comes back as NaN. */
+int psdf_neus_render_backward(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, int max_per_ray,
+    const float* grad_pred, const float* grad_weights_sum, const float* grad_bg_transmittance, const float* sdf, const float* dirs,
+    const float* gradients, const float* dt, const float* rgb, const float* inv_s, float cos_anneal_ratio, int reference_compat,
+    float* grad_sdf, float* grad_gradients, float* grad_rgb, float* grad_inv_s, void* stream);
+/* loss[0] += scale_rgb * sum |pred - gt| hit[ray] + scale_mask * sum BCE(clip(weights_sum, 1e-3, 1 - 1e-3), gt_mask) over
+   nr_rays rays (pred, gt [R,3]; hit [R] bytes or NULL; weights_sum, gt_mask [R]), and the gradients of that sum: grad_pred [R,3]
+   as psdf_l1_loss writes it, grad_weights_sum [R] through the clip (passed on the closed interval, 0 outside); both optional.
+   Deterministic, no floating-point atomics.  workspace: psdf_neus_render_plan's bytes (may be NULL when they are 0). */
+int psdf_neus_mask_loss(int64_t nr_rays, const float* pred, const float* gt, const unsigned char* hit, const float* weights_sum,
+    const float* gt_mask, float scale_rgb, float scale_mask, double* workspace, float* loss, float* grad_pred,
+    float* grad_weights_sum, void* stream);
+
 /* ---- debug query (mlp_bwd.hip) ---- */
 /* Which kernel variant the LAST call of an operator family dispatched to (host only, no device work): lets a parity test
    assert that the configuration it compares with the oracle ran the kernels the benchmark times.  No reference counterpart.

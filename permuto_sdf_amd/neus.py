@@ -121,6 +121,100 @@ def neus_composite(rs, max_per_ray, sdf, gradients, rgb, inv_s, cos_anneal_ratio
     return NeusCompositeFunc.apply(rs, max_per_ray, sdf, gradients, rgb, inv_s, cos_anneal_ratio)
 
 
+# ------------------------------------------------------------------ the render and the loss tail of a masked step
+NEUS_RENDER_PLAN_FIELDS = 4        # PSDF_NEUS_RENDER_PLAN_FIELDS of include/psdf.h
+
+
+def neus_render_plan(nr_rays, max_per_ray=64):
+    """-> (register chunks of the ray backward, workgroups of the loss kernel, bytes of its workspace, the single-group limit),
+    from the library's host-only entry (csrc/neus_render_plan.h decides them)"""
+    out = (L.c_l * NEUS_RENDER_PLAN_FIELDS)()
+    L.call("psdf_neus_render_plan", L.c_l(int(nr_rays)), L.c_i(int(max_per_ray)), out)
+    return tuple(int(v) for v in out)
+
+
+def _check_samples(what, rs, sdf, gradients, rgb):
+    N = sdf.shape[0]
+    if sdf.numel() != N or tuple(gradients.shape) != (N, 3) or (rgb is not None and tuple(rgb.shape) != (N, 3)) \
+            or rs.samples_dirs.shape[0] < N or rs.samples_dt.shape[0] < N:
+        raise ValueError("%s: sdf [N, 1], gradients and rgb [N, 3] over the container's samples; got %s, %s, %s (container: %d)"
+                         % (what, tuple(sdf.shape), tuple(gradients.shape), None if rgb is None else tuple(rgb.shape),
+                            rs.samples_dirs.shape[0]))
+
+
+def neus_render_forward_raw(rs, sdf, gradients, rgb, inv_s, cos_anneal_ratio, want_pred=True, want_weights_sum=True, want_bg=False):
+    """csrc/neus_render.hip: `neus_composite_forward_raw` with the per-ray weight sum -> (pred [R, 3], weights_sum [R, 1], bg
+    transmittance [R, 1]), None for what is not wanted.  Empty and overflowed rays: 0, 0, 1."""
+    if not (want_pred or want_weights_sum or want_bg):
+        raise ValueError("neus_render_forward: nothing is wanted")
+    _check_samples("neus_render_forward", rs, sdf, gradients, rgb if want_pred else None)
+    if inv_s.numel() != 1:
+        raise ValueError("neus_render_forward: inv_s holds one value; got %s" % (tuple(inv_s.shape),))
+    L.require_cuda(sdf, gradients, rgb, inv_s)
+    R, dev = rs.ray_start_end_idx.shape[0], sdf.device
+    f = dict(dtype=torch.float32, device=dev)
+    pred = torch.empty((R, 3), **f) if want_pred else None       # the kernel writes every ray
+    ws = torch.empty((R, 1), **f) if want_weights_sum else None
+    bg = torch.empty((R, 1), **f) if want_bg else None
+    L.call("psdf_neus_render_forward", *rs._ri(), L.ptr(sdf), L.ptr(rs.samples_dirs), L.ptr(gradients), L.ptr(rs.samples_dt),
+           L.ptr(rgb if want_pred else None), L.ptr(inv_s), L.c_f(float(cos_anneal_ratio)), L.ptr(pred), L.ptr(ws), L.ptr(bg), L.stream())
+    return pred, ws, bg
+
+
+def neus_render_backward_raw(rs, max_per_ray, g_pred, g_weights_sum, g_bg, sdf, gradients, rgb, inv_s, cos_anneal_ratio,
+                             need_grad=True, need_rgb=True, need_inv_s=True):
+    """-> g_sdf [N,1], g_gradients [N,3] | None, g_rgb [N,3] | None, g_inv_s [1] | None for the upstream gradients g_pred [R, 3],
+    g_weights_sum [R, 1], g_bg [R, 1]: each may be None (no gradient arrives there), one at least is given.  PsdfError(-2) when a
+    ray may hold more than 256 samples; a ray longer than max_per_ray comes back as NaN."""
+    from .bridge import VolumeRendering, _per_sample
+    if g_pred is None and g_weights_sum is None and g_bg is None:
+        raise ValueError("neus_render_backward: no upstream gradient")
+    R = rs.ray_start_end_idx.shape[0]
+    _check_samples("neus_render_backward", rs, sdf, gradients, rgb if g_pred is not None else None)
+    if (g_pred is not None and tuple(g_pred.shape) != (R, 3)) or any(g is not None and g.numel() != R for g in (g_weights_sum, g_bg)) \
+            or inv_s.numel() != 1:
+        raise ValueError("neus_render_backward: g_pred [R, 3], g_weights_sum and g_bg [R] for the container's %d rays, one inv_s" % R)
+    L.require_cuda(sdf, gradients, rgb, inv_s, g_pred, g_weights_sum, g_bg)
+    N, dev = sdf.shape[0], sdf.device
+    g_sdf = _per_sample(rs, (N, 1), dev)
+    g_grad = _per_sample(rs, (N, 3), dev) if need_grad else None
+    g_rgb = _per_sample(rs, (N, 3), dev) if need_rgb else None
+    g_inv_s = L.zeroed_scalar(dev) if need_inv_s else None
+    L.call("psdf_neus_render_backward", *rs._ri(), L.c_i(int(max_per_ray)), L.ptr(g_pred), L.ptr(g_weights_sum), L.ptr(g_bg),
+           L.ptr(sdf), L.ptr(rs.samples_dirs), L.ptr(gradients), L.ptr(rs.samples_dt), L.ptr(rgb if g_pred is not None else None),
+           L.ptr(inv_s), L.c_f(float(cos_anneal_ratio)), L.c_i(int(VolumeRendering.reference_compat)), L.ptr(g_sdf), L.ptr(g_grad),
+           L.ptr(g_rgb), L.ptr(g_inv_s), L.stream())
+    return g_sdf, g_grad, g_rgb, g_inv_s
+
+
+def neus_mask_loss_raw(pred, gt, hit, weights_sum, gt_mask, mask_weight, loss=None, want_grad=True, workspace=None):
+    """-> (loss [1], g_pred [R, 3] or None, g_weights_sum [R, 1] or None): loss += mean |pred - gt| hit[ray] + mask_weight *
+    mean BCE(clip(weights_sum, 1e-3, 1 - 1e-3), gt_mask), the colour and mask terms of a masked step (train_permuto_sdf.py:
+    372,381-383) and their gradients in one call.  `loss`: the accumulator to ADD to (a fresh zero otherwise).  The same inputs
+    give the same bits on every call.  workspace: float64 [neus_render_plan(R)[2] / 8] to reuse (needed above 8192 rays only)."""
+    if pred.dim() != 2 or pred.shape[1] != 3 or gt.shape != pred.shape:
+        raise ValueError("neus_mask_loss: pred and gt [R, 3]; got %s, %s" % (tuple(pred.shape), tuple(gt.shape)))
+    R = pred.shape[0]
+    if (hit is not None and hit.numel() != R) or weights_sum.numel() != R or gt_mask.numel() != R:
+        raise ValueError("neus_mask_loss: hit, weights_sum and gt_mask hold one entry per ray (%d); got %s, %s, %s"
+                         % (R, None if hit is None else tuple(hit.shape), tuple(weights_sum.shape), tuple(gt_mask.shape)))
+    L.require_cuda(pred, gt, weights_sum, gt_mask)
+    dev = pred.device
+    loss = L.zeroed_scalar(dev) if loss is None else loss
+    g_pred = torch.empty((R, 3), dtype=torch.float32, device=dev) if want_grad else None
+    g_ws = torch.empty((R, 1), dtype=torch.float32, device=dev) if want_grad else None
+    if R == 0:
+        return loss, g_pred, g_ws
+    if workspace is None:
+        nbytes = neus_render_plan(R)[2]
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+    h = None if hit is None else hit.reshape(-1).to(torch.uint8).contiguous()
+    L.call("psdf_neus_mask_loss", L.c_l(R), L.ptr(_c(pred)), L.ptr(_c(gt)), L.ptr(h), L.ptr(_c(weights_sum).reshape(-1)),
+           L.ptr(_c(gt_mask).reshape(-1)), L.c_f(1.0 / (3 * R)), L.c_f(float(mask_weight) / R), L.ptr(workspace), L.ptr(loss),
+           L.ptr(g_pred), L.ptr(g_ws), L.stream())
+    return loss, g_pred, g_ws
+
+
 def l1_loss_raw(pred, gt, mask=None, scale=None, want_grad=True, loss=None):
     """-> (loss [1], g_pred or None): loss = scale * sum |gt - pred| * mask; scale defaults to 1/numel (the reference's mean).
     `loss`: an accumulator to ADD to (the kernels add with one atomic per workgroup) instead of a fresh zero"""

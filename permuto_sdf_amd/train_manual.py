@@ -13,6 +13,9 @@ What is differentiated (train_permuto_sdf.py:311-429, run_net :111-169; names as
   encoding's position backward);  colour = sigmoid(Lipshitz-MLP([enc2(p), SH5(dir), normalize(n), geom]));
   (radiance, bgT) = NeuS(sdf, n, colour);  bg samples -> NerfHash -> radiance_bg;  pred = radiance + bgT * radiance_bg;
   loss = L1(pred, gt) + w_e eikonal(n) + w_c curvature(n, n(p + eps cross(norm n, norm r))) + w_o offsurface(sdf(p_off)) [+ Lipschitz].
+A `--with_mask` run (train_permuto_sdf.py:153-154,381-383) has no background branch: pred = radiance, and the loss gains
+w_m BCE(clip(sum of the NeuS weights per ray, 1e-3, 1 - 1e-3), mask): the render with that sum and the colour + mask loss tail are
+csrc/neus_render.hip (`_masked_render_and_loss`; tests/test_gpu_train_mask_step.py holds it against the autograd trainer).
 The backward of  n = d sdf / d p  is the double backward: `psdf_encode_double_backward` (gradient w.r.t. the lattice and w.r.t.
 the feature gradient) -> `psdf_mlp_double_backward` (gradient w.r.t. features and parameters) -> the encoding's lattice backward.
 `tests/test_gpu_train_step.py::test_manual_backward_equals_autograd` holds every gradient of this file against the autograd
@@ -33,7 +36,8 @@ from .mlp import (_grad_views, double_backward_plus_supported, mlp_forward_wide_
                   mlp_forward_raw, pack_params)
 from .net_eval import enc_backward, enc_forward, net_params, sdf_gradient, sdf_gradient_backward, set_grads
 from .neus import (eikonal_loss_raw, l1_loss_raw, nerf_composite_backward_raw, nerf_composite_forward_raw, neus_composite_backward_raw,
-                   neus_composite_forward_raw, sigmoid_rows_backward_raw, sigmoid_rows_raw)
+                   neus_composite_forward_raw, neus_mask_loss_raw, neus_render_backward_raw, neus_render_forward_raw,
+                   sigmoid_rows_backward_raw, sigmoid_rows_raw)
 from .train_step import Trainer
 
 
@@ -46,10 +50,11 @@ def _normalize3(x, gy=None):
 class _Step:
     """What `_main_forward` hands to `_main_backward`: every field exists from the start, None until its stage has run, so the
     backward tests the field (calib, g_cw_bg, g_cb_bg: colour calibration; fg, g_n: foreground samples; curv: curvature weight
-    > 0) and not the condition the forward ran under.  calib, net, bg, fg, curv are small records (SimpleNamespace), each built
+    > 0; g_ws: the weight sum's gradient of a masked step, which has no bg, g_bgT, g_cw_bg, g_cb_bg) and not the condition the
+    forward ran under.  calib, net, bg, fg, curv are small records (SimpleNamespace), each built
     in one place: `_calib_build`, `_main_forward`, `_bg_forward`, `_fg_forward`, `_curvature_forward`."""
     __slots__ = ("it", "R", "n_fg", "loss", "calib", "net", "inv_s", "cos_r", "arena", "bg", "fg", "curv", "off", "feat_o",
-                 "g_pred", "g_bgT", "g_n", "g_cw_bg", "g_cb_bg")
+                 "g_pred", "g_bgT", "g_ws", "g_n", "g_cw_bg", "g_cb_bg")
 
     def __init__(self, **kw):
         for name in self.__slots__:
@@ -151,12 +156,14 @@ class ManualTrainer(Trainer):
 
     def _hand_written_step_applies(self):
         """The hand-written step is built on the fused compositing kernels (at most 256 samples per ray: foreground
-        max_nr_samples_per_ray + 2 * nr_samples_imp_sampling, background nr_samples_bg) and on the reference's default mode
-        (background network, no mask loss).  Anything else runs `Trainer._main_phase`: the same step as an autograd graph over
-        the per-operator chain -- slower, any ray length, `--with_mask` included."""
+        max_nr_samples_per_ray + 2 * nr_samples_imp_sampling, background nr_samples_bg).  Both of the reference's modes run it:
+        the default one (background network, csrc/composite_fused.hip) and `--with_mask` (no background: only the foreground
+        bound applies; the render with the per-ray weight sum and the colour + mask loss tail of csrc/neus_render.hip).
+        Anything else runs `Trainer._main_phase`: the same step as an autograd graph over the per-operator chain -- slower, any
+        ray length."""
         hp = self.hp
-        return (not self.with_mask and hp.nr_samples_bg <= 256
-                and hp.max_nr_samples_per_ray + 2 * hp.nr_samples_imp_sampling <= 256)
+        fg_fits = hp.max_nr_samples_per_ray + 2 * hp.nr_samples_imp_sampling <= 256
+        return fg_fits if self.with_mask else (fg_fits and hp.nr_samples_bg <= 256)
 
     # ------------------------------------------------------------------ the SDF network, one evaluation
     def _sdf_gradient(self, feat, pts, net):
@@ -243,8 +250,12 @@ class ManualTrainer(Trainer):
     def _calib_assign_grads(self, calib, g_cw_bg, g_cb_bg, g_cw, g_cb):
         """per-ray gradients of both branches (the foreground's None without foreground samples) -> weight_delta.grad, bias.grad"""
         cc = self.colorcal
-        g_cw = g_cw_bg if g_cw is None else g_cw_bg + g_cw         # background first: the order the sums have always been taken in
-        g_cb = g_cb_bg if g_cb is None else g_cb_bg + g_cb
+        if g_cw_bg is None:                                        # a masked step: the foreground's alone ...
+            if g_cw is None:                                       # ... and nothing without foreground samples (step() fills zeros)
+                return
+        else:
+            g_cw = g_cw_bg if g_cw is None else g_cw_bg + g_cw     # background first: the order the sums have always been taken in
+            g_cb = g_cb_bg if g_cb is None else g_cb_bg + g_cb
         fixed3 = calib.fixed.expand(-1, 3)
         gwd = torch.zeros_like(cc.weight_delta).index_add_(0, calib.cam, torch.where(fixed3, torch.zeros_like(g_cw), g_cw))
         gbi = torch.zeros_like(cc.bias).index_add_(0, calib.cam, torch.where(fixed3, torch.zeros_like(g_cb), g_cb))
@@ -252,8 +263,9 @@ class ManualTrainer(Trainer):
 
     # ------------------------------------------------------------------ the foreground branch: SDF net, colour net, NeuS compositing
     def _fg_forward(self, st, fgs):
-        """-> (pred_fg [R, 3], bgT [R, 1]); st.fg: what the curvature term and the backward need (c_enc, c_sh: row offsets in
-        x_rgb = [colour encoding | SH | normal | geometry features]; rgb_raw, ridx: None without calibration)"""
+        """-> (pred_fg [R, 3], bgT [R, 1]), a masked step: (pred [R, 3], weights_sum [R, 1]); st.fg: what the curvature term and
+        the backward need (c_enc, c_sh: row offsets in x_rgb = [colour encoding | SH | normal | geometry features]; rgb_raw, ridx:
+        None without calibration)"""
         net, rgbn = st.net, self.rgb
         pts = fgs.samples_pos
         feat = enc_forward(self.sdf.encoding, pts, net.win)
@@ -273,6 +285,9 @@ class ManualTrainer(Trainer):
         rgb, rgb_raw, ridx = _calib_sigmoid(st.calib, rgb_fm, fgs.ray_start_end_idx)
         st.fg = SimpleNamespace(samples=fgs, pts=pts, feat=feat, dfeat=dfeat, e0=e0, n=n, sdf_col=y[0].view(-1, 1), x_rgb=x_rgb,
                                 c_enc=feat2.shape[0], c_sh=feat2.shape[0] + sh.shape[1], wn=wn, bsr=bsr, rgb=rgb, rgb_raw=rgb_raw, ridx=ridx)
+        if self.with_mask:                 # no background behind it: the radiance IS the prediction, the weight sum feeds the mask loss
+            pred, ws, _ = neus_render_forward_raw(fgs, st.fg.sdf_col, n, rgb, st.inv_s, st.cos_r)
+            return pred, ws
         pred_fg, bgT, _ = neus_composite_forward_raw(fgs, st.fg.sdf_col, n, rgb, st.inv_s, st.cos_r)
         return pred_fg, bgT
 
@@ -281,8 +296,12 @@ class ManualTrainer(Trainer):
         SDF net's outputs, through the SDF net once -> (g_cw, g_cb) of the colour calibration (or None, None)"""
         fg, net, hp, rgbn, m = st.fg, st.net, self.hp, self.rgb, self.rgb.mlp
         per_ray = hp.max_nr_samples_per_ray + 2 * hp.nr_samples_imp_sampling
-        g_sdf, g_nc, g_rgb, _ = neus_composite_backward_raw(fg.samples, per_ray, st.g_pred.contiguous(), st.g_bgT.contiguous(), fg.sdf_col,
-                                                            fg.n, fg.rgb, st.inv_s, st.cos_r, need_grad=True, need_rgb=True, need_inv_s=False)
+        if st.g_ws is not None:            # a masked step: gradients of the colour and of the weight sum, none of the bg transmittance
+            g_sdf, g_nc, g_rgb, _ = neus_render_backward_raw(fg.samples, per_ray, st.g_pred, st.g_ws, None, fg.sdf_col, fg.n, fg.rgb,
+                                                             st.inv_s, st.cos_r, need_grad=True, need_rgb=True, need_inv_s=False)
+        else:
+            g_sdf, g_nc, g_rgb, _ = neus_composite_backward_raw(fg.samples, per_ray, st.g_pred.contiguous(), st.g_bgT.contiguous(), fg.sdf_col,
+                                                                fg.n, fg.rgb, st.inv_s, st.cos_r, need_grad=True, need_rgb=True, need_inv_s=False)
         g_pre_fm, g_cw, g_cb = _calib_sigmoid_backward(st.calib, g_rgb, fg.rgb, fg.rgb_raw, fg.ridx)
         dXr, dWn, dbr = mlp_backward_raw(m.dims, fg.x_rgb, fg.wn, fg.bsr, g_pre_fm, need_dx=True, into=st.arena[2])
         dws, dcs = lipshitz_normalize_all_backward_raw(m.weights_per_layer, m.lipshitz_bound_per_layer, dWn, dc_flat=st.arena[3])
@@ -301,6 +320,17 @@ class ManualTrainer(Trainer):
             dX1, _, _ = mlp_backward_raw(net.dims, fg.feat, net.ws, net.bs, g_y, need_dx=True, into=(net.gb.dWs, net.gb.dbs))
             self._sdf_gradient_backward(g_n, fg.feat, fg.dfeat, fg.e0, fg.pts, net, extra_dfeat=dX1)
         return g_cw, g_cb
+
+    def _masked_render_and_loss(self, st, fgs, gt, hit, gt_mask):
+        """The `--with_mask` form of render + colour loss (train_permuto_sdf.py:153-154,372,381-383): the foreground's radiance is
+        the prediction, its per-ray weight sum is held to the mask.  One render launch and ONE loss launch that adds both terms
+        to st.loss and leaves st.g_pred, st.g_ws.  Without foreground samples the render is 0, 0: the tail still runs (its value
+        is part of the loss), nothing flows back."""
+        if st.n_fg:
+            pred, ws = self._fg_forward(st, fgs)
+        else:
+            pred, ws = torch.zeros(st.R, 3, device=self.dev), torch.zeros(st.R, 1, device=self.dev)
+        _, st.g_pred, st.g_ws = neus_mask_loss_raw(pred, gt, hit, ws, gt_mask, self.hp.mask_weight, loss=st.loss)
 
     # ------------------------------------------------------------------ curvature term: n against n at a point 1e-4 along a tangent
     def _curvature_forward(self, st, weight):
@@ -371,14 +401,18 @@ class ManualTrainer(Trainer):
         right behind them its lattice's reduction (data parallel) overlaps all the rest -- the background is finished when this
         returns, `_main_backward` is the foreground's and the off-surface points'."""
         hp, dev, sdfn = self.hp, self.dev, self.sdf
-        (o, d, gt, hit, img_idx, _), begun = self._step_rays(reel, git)
+        (o, d, gt, hit, img_idx, gt_mask), begun = self._step_rays(reel, git)
         st = _Step(it=it, R=o.shape[0], calib=self._calib_build(img_idx),
                    cos_r=map_range_val(it, 0.0, hp.forced_variance_finish_iter, 0.0, 1.0))
         # the background network's forward is enqueued from the hook, while the host waits for the march's sample counts (it needs
         # the background samples only), so the step's one host sync leaves no bubble on the GPU
-        fgs, bgs = self._samples(o, d, it, True, begun=begun, between=lambda bg_: setattr(st, "bg", self._bg_forward(bg_, st.calib)))
-        if st.bg is None:                  # (a sampler replaced from outside that left the hook alone)
-            st.bg = self._bg_forward(bgs, st.calib)
+        if self.with_mask:                 # no background samples, no background network: nothing to enqueue meanwhile
+            fgs, bgs = self._samples(o, d, it, True, begun=begun)
+            self._params_ready(2)          # (the background lattice is not read: its gather of the previous step is retired here)
+        else:
+            fgs, bgs = self._samples(o, d, it, True, begun=begun, between=lambda bg_: setattr(st, "bg", self._bg_forward(bg_, st.calib)))
+            if st.bg is None:              # (a sampler replaced from outside that left the hook alone)
+                st.bg = self._bg_forward(bgs, st.calib)
         st.n_fg = fgs.samples_pos.shape[0]
         self._params_ready(0)              # the SDF lattice's parameters, before anything below reads them (data parallel)
         dims, _, ws, bs = net_params(sdfn.mlp_sdf)
@@ -393,17 +427,22 @@ class ManualTrainer(Trainer):
         st.loss = L.zeroed_scalar(dev)     # ONE accumulator: every loss kernel of the step adds its (already weighted) term to it
         self._pos_pool = None              # (zero-filled position gradients: a fresh pool per step)
         st.arena = self._grad_arena()      # zero-filled parameter gradients of the nets without a persistent buffer: one fill
-        if st.n_fg:
-            pred_fg, bgT = self._fg_forward(st, fgs)
+        if self.with_mask:
+            self._masked_render_and_loss(st, fgs, gt, hit, gt_mask)
         else:
-            pred_fg, bgT = torch.zeros(st.R, 3, device=dev), torch.ones(st.R, 1, device=dev)
-        # softplus -> opacity -> transmittance -> weights -> background radiance -> pred = pred_fg + bgT * pred_bg: one launch
-        _, pred = nerf_composite_forward_raw(bgs, st.bg.raw_den, st.bg.rgbb, pred_fg, bgT)
-        _, st.g_pred = l1_loss_raw(pred, gt, hit, loss=st.loss)
-        # pred = pred_fg + bgT * pred_bg and the whole background compositing backward, one launch
-        g_raw, g_rgbb, st.g_bgT = nerf_composite_backward_raw(bgs, hp.nr_samples_bg, st.g_pred, st.bg.raw_den, st.bg.rgbb, bgT)
-        st.g_cw_bg, st.g_cb_bg = self._bg_backward(st.bg, g_raw, g_rgbb, st.calib, st.arena[0], st.arena[1])
-        self._dp_lattice_final(2)          # right after the background backward: its lattice's reduction overlaps what follows
+            if st.n_fg:
+                pred_fg, bgT = self._fg_forward(st, fgs)
+            else:
+                pred_fg, bgT = torch.zeros(st.R, 3, device=dev), torch.ones(st.R, 1, device=dev)
+            # softplus -> opacity -> transmittance -> weights -> background radiance -> pred = pred_fg + bgT * pred_bg: one launch
+            _, pred = nerf_composite_forward_raw(bgs, st.bg.raw_den, st.bg.rgbb, pred_fg, bgT)
+            _, st.g_pred = l1_loss_raw(pred, gt, hit, loss=st.loss)
+            # pred = pred_fg + bgT * pred_bg and the whole background compositing backward, one launch
+            g_raw, g_rgbb, st.g_bgT = nerf_composite_backward_raw(bgs, hp.nr_samples_bg, st.g_pred, st.bg.raw_den, st.bg.rgbb, bgT)
+            st.g_cw_bg, st.g_cb_bg = self._bg_backward(st.bg, g_raw, g_rgbb, st.calib, st.arena[0], st.arena[1])
+        # right after the background backward: its lattice's reduction overlaps what follows (a masked step: the buffer is zero
+        # and final from the start; the collective keeps its place so that every rank issues the same sequence)
+        self._dp_lattice_final(2)
         if st.n_fg:
             _, st.g_n = eikonal_loss_raw(st.fg.n, scale=eikonal_weight / st.n_fg, loss=st.loss)
             gw = map_range_val(it, hp.iter_start_reduce_curv, hp.iter_finish_reduce_curv, 1.0, 0.0)
