@@ -948,6 +948,22 @@ int psdf_box_trace_resolve(int nr_rays, int stride, const float* origins, const 
     sdf_end, const float* gradients, const uint8_t* no_hit, float coverage_thresh, const float* rot_cam_world, int H, int W,
     int64_t pixel_first, float* normals_img, float* normals_cam_img, float* weights_sum_img, float* depth_img, void* stream);
 
+/* ---- frame_composite.hip: views of a NeRF ---- */
+/* replaces: train_nerf.py:66-71,92-128 -- per chunk, NerfHash's softplus, VolumeRenderingNerf.compute_weights + integrate of
+   the FOREGROUND as run_net calls them, and the list appends, torch.cat and lin2nchw of run_net_in_chunks around it.  Ray-index
+   and sample arguments as psdf_nerf_render_forward; z [M] the samples' depth along their ray; H, W, pixel_first as in the
+   section below.  Written at pixel pixel_first + ray: rgb_img [3, H, W] <- sum w rgb; weights_sum_img [1, H, W] <- sum w;
+   depth_img [1, H, W] or NULL <- sum w z, summed as a colour channel is (not in the reference; with NULL z is not read and may
+   be NULL); transmittance [nr_rays] <- T of the ray's last sample, what psdf_frame_composite_nerf of the same chunk reads.
+   The sweep and the order of summation are psdf_nerf_render_forward's: the planes hold its bits.  Empty and overflowed rays: 0,
+   0, 0 and 1.  Any ray length.  With max_nr_samples = 0 the sample pointers may be NULL.  Allocates nothing and never
+   synchronises; nr_rays <= 0 returns 0 before any pointer check; -1 for a NULL required pointer (z with depth_img and
+   max_nr_samples > 0 among them), max_nr_samples < 0, equal with fixed < 0, an extent < 1 or a range outside the frame; -2 for
+   H W >= 2^31 */
+int psdf_nerf_frame_render(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, const float*
+    raw_density, const float* dt, const float* z, const float* rgb, int H, int W, int64_t pixel_first, float* rgb_img, float*
+    weights_sum_img, float* depth_img, float* transmittance, void* stream);
+
 /* ---- frame_rays.hip, frame_composite.hip ---- */
 /* A held-out view rendered volumetrically, a chunk of pixels at a time, into planar [3, H, W] / [1, H, W] fp32 images on the
    device.  Pixel p of an H x W frame is (x, y) = (p % W, p / W) with its centre at +0.5; a chunk is the pixel range

@@ -8,10 +8,11 @@ from . import image_eval
 from . import render
 from . import sdf_fit
 from . import nerf_train
+from . import nerf_view
 from . import box_trace
 from .box_trace import Box, BoxPlayer, BoxTracedFrame, BoxTracer, render_box_traced
 from .encoding import PermutoEncoding, Coarse2Fine
 from .mlp import FusedMLP, LipshitzMLP
 
-__all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval", "render", "sdf_fit", "nerf_train", "box_trace",
-           "Box", "BoxTracer", "BoxPlayer", "BoxTracedFrame", "render_box_traced"]
+__all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval", "render", "sdf_fit", "nerf_train", "nerf_view",
+           "box_trace", "Box", "BoxTracer", "BoxPlayer", "BoxTracedFrame", "render_box_traced"]

@@ -19,6 +19,14 @@
 // HBM traffic: 44 B per sample read (sdf 4, dirs 12, gradients 12, dt 4, rgb 12) and nothing written per sample; per ray 8 B
 // of range read, 4 B of transmittance and 40 B of planes written (52 B with camera normals).  The background kernel reads 20 B
 // per sample (raw density 4, dt 4, rgb 12) and per ray 8 + 4 + 12 B, and writes 24 B.
+//
+// A NeRF foreground (permuto_sdf_py/train_nerf.py: run_net :66-71 per chunk, run_net_in_chunks :92-128 around it) has no surface
+// and so no normal plane.  frame_render_nerf_kernel renders its container with the sweep, the opacity and the order of summation
+// of nerf_render_fwd_kernel (nerf_render.hip) -- the planes hold the bits of psdf_nerf_render_forward -- and adds the expected
+// depth sum w z, summed as a colour channel is, from the same sweep; it leaves the transmittance buffer that
+// frame_composite_nerf_kernel reads.  HBM traffic: 20 B per sample read (raw density 4, dt 4, rgb 12), 24 B with the depth
+// plane (z 4), nothing written per sample; per ray 8 B of range read, 4 B of transmittance and 16 B of planes written (20 B
+// with the depth plane).
 // Any ray length; no LDS; nothing allocates and nothing synchronises.
 #include "composite_device.h"
 #include "frame_plan.h"
@@ -130,6 +138,43 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   }
 }
 
+__global__ void __launch_bounds__(PSDF_BLOCK)
+    frame_render_nerf_kernel(int nr_rays, RayIndex ri, const float* __restrict__ raw, const float* __restrict__ dt,
+                             const float* __restrict__ z, const float* __restrict__ rgb, int64_t plane, int64_t pixel_first,
+                             float* __restrict__ rgb_img, float* __restrict__ weights_sum_img, float* __restrict__ depth_img,
+                             float* __restrict__ transmittance) {
+  const int lane = lane_id();
+  RAY_LOOP(ray, nr_rays) {
+    int s, e;
+    ri.get(ray, s, e);
+    float r = 0.f, g = 0.f, b = 0.f, ws = 0.f, dz = 0.f, T_bg = 1.f;   // an empty / overflowed ray renders nothing
+    if (ri.valid(s, e)) {
+      T_bg = sweep(
+          s, e - s, lane, [&](int64_t m) { return nerf_alpha(raw[m], dt[m]).a; },
+          [&](int64_t m, float a, float T) {
+            const float w = a * T;
+            ws += w;
+            r += w * rgb[3 * m];
+            g += w * rgb[3 * m + 1];
+            b += w * rgb[3 * m + 2];
+            if (depth_img) dz += w * z[m];
+          });
+      r = wave_sum(r);
+      g = wave_sum(g);
+      b = wave_sum(b);
+      ws = wave_sum(ws);
+      if (depth_img) dz = wave_sum(dz);     // (a kernel argument: the whole wave takes the branch or none of it)
+    }
+    if (lane == 0) {
+      const int64_t pixel = pixel_first + ray;
+      st_planes(rgb_img, plane, pixel, mk3(r, g, b));
+      weights_sum_img[pixel] = ws;
+      if (depth_img) depth_img[pixel] = dz;
+      transmittance[ray] = T_bg;
+    }
+  }
+}
+
 // the pixel range [pixel_first, pixel_first + nr_rays) of an H x W frame: 0, or the code to return
 inline int check_range(int nr_rays, int H, int W, int64_t pixel_first) {
   if (H < 1 || W < 1) return PSDF_ERR_ARG;
@@ -175,6 +220,23 @@ int psdf_frame_composite_nerf(int nr_rays, const int* start_end, int equal, int 
   hipLaunchKernelGGL(frame_composite_nerf_kernel, dim3(ray_grid(nr_rays)), dim3(PSDF_BLOCK), 0, (hipStream_t)stream, nr_rays,
                      RayIndex{start_end, equal, fixed, max_nr_samples}, raw_density, dt, rgb, transmittance, (int64_t)H * W,
                      pixel_first, rgb_img, rgb_bg_img);
+  PSDF_LAUNCH_CHECK();
+  return PSDF_OK;
+}
+
+int psdf_nerf_frame_render(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, const float* raw_density,
+                           const float* dt, const float* z, const float* rgb, int H, int W, int64_t pixel_first, float* rgb_img,
+                           float* weights_sum_img, float* depth_img, float* transmittance, void* stream) {
+  if (nr_rays <= 0) return PSDF_OK;
+  if (!rgb_img || !weights_sum_img || !transmittance || (!equal && !start_end)) return PSDF_ERR_ARG;
+  if (max_nr_samples < 0 || (equal && fixed < 0)) return PSDF_ERR_ARG;
+  // a container without samples may come without sample tensors; z is read for the depth plane alone
+  if (max_nr_samples > 0 && (!raw_density || !dt || !rgb || (depth_img && !z))) return PSDF_ERR_ARG;
+  const int status = check_range(nr_rays, H, W, pixel_first);
+  if (status != PSDF_OK) return status;
+  hipLaunchKernelGGL(frame_render_nerf_kernel, dim3(ray_grid(nr_rays)), dim3(PSDF_BLOCK), 0, (hipStream_t)stream, nr_rays,
+                     RayIndex{start_end, equal, fixed, max_nr_samples}, raw_density, dt, z, rgb, (int64_t)H * W, pixel_first,
+                     rgb_img, weights_sum_img, depth_img, transmittance);
   PSDF_LAUNCH_CHECK();
   return PSDF_OK;
 }

@@ -22,7 +22,8 @@ the FOREGROUND (radiance, weight sum, background transmittance) with their gradi
 
 Left out: the per-image colour calibration (train_nerf.py:52,158-159; `Colorcal`) -- `NerfTrainer(colorcal=...)` raises before
 it touches a device --, the viewer branches and the dataset loaders.  The bounding primitive is the tree's `Sphere` of radius
-0.5 (the reference builds an axis-aligned box per dataset, which the tree does not have); the occupancy grid spans [-0.5, 0.5]^3.
+0.5, as in the reference (create_bb_for_dataset returns Sphere(0.5) for every dataset name, common_utils.py:508-528); the
+occupancy grid spans [-0.5, 0.5]^3.  Views of a trained run as image planes: nerf_view.py (`NerfTrainer.renderer()`).
 """
 import contextlib
 import os
@@ -344,13 +345,22 @@ class NerfTrainer:
         it = self.iter if it is None else it
         parallel.seed_generators(parallel.step_seed(self._seed, 0, it, world=1), self.dev)
         o, d, gt, gt_mask, _ = PermutoSDF.random_rays_from_reel(reel, hp.nr_rays)
+        hit, fg, bg = self.sample(o, d, True)
+        return SimpleNamespace(gt=gt, gt_mask=gt_mask, hit=hit, fg=fg, bg=bg, R=o.shape[0], n_fg=fg.samples_pos.shape[0])
+
+    @torch.no_grad()
+    def sample(self, o, d, jitter):
+        """create_samples (nerf_utils.py:502-526) -> (hits of the bounding sphere, the foreground container (compacted: one host
+        wait), the background container (None under with_mask)); jitter: model.training.  Reads `sphere`, `grid`, `hp` and
+        `with_mask` alone: nerf_view.NerfFrameRenderer calls it for models that come without a trainer."""
+        hp = self.hp
         _, te, _, tx, hit = self.sphere.ray_intersection(o, d)
         fg = self.grid.compute_samples_in_occupied_regions(o, d, te, tx, hp.min_dist_between_samples, hp.max_nr_samples_per_ray,
-                                                           True).compact_to_valid_samples()
+                                                           jitter).compact_to_valid_samples()
         bg = None
         if not self.with_mask:
-            bg = RaySampler.compute_samples_bg(o, d, tx, hp.nr_samples_bg, self.sphere.m_radius, self.sphere.m_center, True, False)
-        return SimpleNamespace(gt=gt, gt_mask=gt_mask, hit=hit, fg=fg, bg=bg, R=o.shape[0], n_fg=fg.samples_pos.shape[0])
+            bg = RaySampler.compute_samples_bg(o, d, tx, hp.nr_samples_bg, self.sphere.m_radius, self.sphere.m_center, jitter, False)
+        return hit, fg, bg
 
     # ---- one net, by hand
     def _grad_arena(self):
@@ -362,10 +372,11 @@ class NerfTrainer:
         return views
 
     @staticmethod
-    def _branch_forward(net, pts, dirs, it):
-        """lattice -> density + feature net -> [gelu(features); SH4(dir)] (one launch) -> colour head -> sigmoid"""
+    def _branch_forward(net, pts, dirs, it, train=True):
+        """lattice -> density + feature net -> [gelu(features); SH4(dir)] (one launch) -> colour head -> sigmoid.  train=False
+        (rendering): the lattice rows read are not marked for the optimiser"""
         win = net.window(it).contiguous()
-        feat = enc_forward(net.encoding, pts, win)
+        feat = enc_forward(net.encoding, pts, win, train)
         net1 = d1, _, w1, b1 = net_params(net.mlp_feat_and_density)
         fd = mlp_forward_wide_f16_raw(d1, feat, w1, b1)                      # [65, M] on the fp16 matrix pipe
         if fd is None:      # (the library declined: fp32 MFMAs)
@@ -469,6 +480,11 @@ class NerfTrainer:
         self.iter += 1
         self.last = {"nr_rays": b.R, "nr_fg_samples": b.n_fg}
         return loss
+
+    def renderer(self):
+        """-> nerf_view.NerfFrameRenderer over this trainer's nets, grid and sphere: views of a camera as image planes"""
+        from .nerf_view import NerfFrameRenderer
+        return NerfFrameRenderer(self)
 
     # ---- checkpoints: the reference's nerf_hash_model.pt / nerf_hash_model_bg.pt and the two grid tensors (train_nerf.py:230-238)
     def save_checkpoint(self, folder):

@@ -119,13 +119,17 @@ def raw(enc):
     lat = enc._parameters["lattice_values"]
     r = enc.__dict__.get("_psdf_raw")
     if r is None or r[5] != lat.data_ptr() or r[4] is not enc.__dict__.get("touched_rows"):
-        r = (enc.cfg, lat.detach(), enc.scale_factor, enc.random_shift_per_level.detach(), enc.touched_rows, lat.data_ptr())
+        r = (enc.cfg, lat.detach(), enc.scale_factor, enc.random_shift_per_level.detach(), enc.__dict__.get("touched_rows"),
+             lat.data_ptr())
         enc.__dict__["_psdf_raw"] = r
     return r
 
 
 def enc_forward(enc, pts, win, train=True, out=None):
+    """train=False: the lattice is read and no row is marked (an encoding without a touched-rows record can be evaluated so)"""
     cfg, lat, sf, sh, tr, _ = raw(enc)
+    if not train:
+        return encode_forward_raw(cfg, pts, lat, sf, sh, win, out=out)
     return encode_forward_raw(cfg, pts, lat, sf, sh, win, out=out, touched=tr.touched if train else None,
                               block_rows_log2=tr.block_rows_log2)
 
