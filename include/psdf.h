@@ -948,6 +948,38 @@ int psdf_box_trace_resolve(int nr_rays, int stride, const float* origins, const 
     sdf_end, const float* gradients, const uint8_t* no_hit, float coverage_thresh, const float* rot_cam_world, int H, int W,
     int64_t pixel_first, float* normals_img, float* normals_cam_img, float* weights_sum_img, float* depth_img, void* stream);
 
+/* ---- colorcal.hip ---- */
+/* Per-image colour calibration of NeRF training (permuto_sdf_py/train_nerf.py:52,158-161; Colorcal, models.py:678-729), applied
+   to the raw colours of a packed container before the sigmoid (models.py:520-523).  Ray-index arguments as
+   psdf_nerf_render_forward (the compacted form and the equal-count form with implicit ranges); nr_samples M; img_idx [R] int32
+   the image of every ray; weight_delta, bias [nr_images, 3].  A ray of image idx_fixed, and a ray whose img_idx lies outside
+   [0, nr_images), keeps the identity (w = 1, b = 0) and the tables are not read for it.  A ray is processed when RayIndex
+   accepts it and its range lies inside [0, M].  The entries allocate nothing and never synchronise; nr_rays <= 0 returns 0
+   before any pointer is looked at (nothing is written).  -1: nr_samples < 0, nr_images < 1, idx_fixed outside [0, nr_images), a
+   NULL pointer that is needed; -2: nr_rays > 2^31 - 1 - 2^18, nr_samples > (2^31 - 1) / 3, nr_images > 2^24. */
+/* replaces: Colorcal.calib_RGB_samples_packed (models.py:693-729) + the sigmoid (models.py:520-523) on the colour head's
+   feature-major output raw_fm [3, M] -> rgb [M, 3] = 1 / (1 + expf(-z)), z = raw * (1 + weight_delta[img]) rounded, + bias[img]
+   rounded.  With w = 1, b = 0 the bits of psdf_sigmoid_rows.  Slots no processed ray owns are not written.  nr_samples == 0
+   returns 0 as well. */
+int psdf_colorcal_sigmoid_forward(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, int64_t nr_samples,
+    const float* raw_fm, const int* img_idx, int nr_images, int idx_fixed, const float* weight_delta, const float* bias, float*
+    rgb, void* stream);
+/* Backward of the above for grad_rgb [M, 3], with rgb [M, 3] (the forward's output) and raw_fm [3, M]: grad_raw_fm [3, M] <-
+   g_pre w, g_pre = grad_rgb rgb (1 - rgb) (slots no processed ray owns are not written); grad_ray [R, 6] <- per ray the sums
+   over its samples of g_pre raw (columns 0-2) and of g_pre (columns 3-5).  Every row of grad_ray is written: zeros for rays that
+   are not processed and for rays that keep the identity.  The order of a ray's sums depends on its sample count alone (16
+   lanes take the samples in turn, then a fixed butterfly): no atomics, the same inputs give the same bits on every call.  With
+   nr_samples == 0 the sample pointers and the tables may be NULL. */
+int psdf_colorcal_sigmoid_backward(int nr_rays, const int* start_end, int equal, int fixed, int max_nr_samples, int64_t nr_samples,
+    const float* grad_rgb, const float* rgb, const float* raw_fm, const int* img_idx, int nr_images, int idx_fixed, const float*
+    weight_delta, const float* bias, float* grad_raw_fm, float* grad_ray, void* stream);
+/* replaces: the two index_add_ of torch autograd through Colorcal's index_select.  grad_ray_a [R, 6], grad_ray_b [R, 6] or NULL
+   (a second branch: the background's) -> grad_weight_delta [nr_images, 3] <- for every image the sum over its rays, in
+   ascending ray order, of (grad_ray_b[r] + grad_ray_a[r]) columns 0-2, grad_bias [nr_images, 3] <- of columns 3-5.  Every entry
+   is written; the row of idx_fixed and of an image no ray drew is exactly 0.  Deterministic. */
+int psdf_colorcal_fold(int nr_rays, const int* img_idx, int nr_images, int idx_fixed, const float* grad_ray_a, const float*
+    grad_ray_b, float* grad_weight_delta, float* grad_bias, void* stream);
+
 /* ---- frame_composite.hip: views of a NeRF ---- */
 /* replaces: train_nerf.py:66-71,92-128 -- per chunk, NerfHash's softplus, VolumeRenderingNerf.compute_weights + integrate of
    the FOREGROUND as run_net calls them, and the list appends, torch.cat and lin2nchw of run_net_in_chunks around it.  Ray-index

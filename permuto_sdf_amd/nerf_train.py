@@ -20,8 +20,11 @@ the FOREGROUND (radiance, weight sum, background transmittance) with their gradi
                          nerf_alpha -> cumprod -> multiply -> integrate -> sum_over_each_ray and torch's loss; the yardstick
                          the hand-written step is held against, not a fallback).
 
-Left out: the per-image colour calibration (train_nerf.py:52,158-159; `Colorcal`) -- `NerfTrainer(colorcal=...)` raises before
-it touches a device --, the viewer branches and the dataset loaders.  The bounding primitive is the tree's `Sphere` of radius
+  * `colorcal_sigmoid`   the per-image colour calibration of train_nerf.py:52,158-161 (`Colorcal`, models.py:678-729) with the
+                         sigmoid behind it, csrc/colorcal.hip: one launch forward, one backward and one fold of the per-ray
+                         sums into the two [I, 3] gradients, deterministic; `NerfTrainer(nr_images=...)` trains with it.
+
+Left out: the viewer branches and the dataset loaders.  The bounding primitive is the tree's `Sphere` of radius
 0.5, as in the reference (create_bb_for_dataset returns Sphere(0.5) for every dataset name, common_utils.py:508-528); the
 occupancy grid spans [-0.5, 0.5]^3.  Views of a trained run as image planes: nerf_view.py (`NerfTrainer.renderer()`).
 """
@@ -41,13 +44,15 @@ from .net_eval import enc_backward, enc_forward, net_params, one_row_head, scala
 from .neus import (nerf_alpha, nerf_composite, nerf_composite_backward_raw, nerf_composite_forward_raw, sigmoid_rows_backward_raw,
                    sigmoid_rows_raw)
 from .optim import FusedAdamW
-from .train_step import BgNet, _Cumprod, _Integrate, _SumRay, _lattice, cat_fm
+from .train_step import BgNet, Colorcal, _Cumprod, _Integrate, _SumRay, _lattice, cat_fm
 
 PLAN_FIELDS = 4                    # PSDF_NERF_RENDER_PLAN_FIELDS of include/psdf.h
 FUSED_MAX_PER_RAY = 256
 MASK_WEIGHT = 0.1                  # train_nerf.py:207
 CLIP_LO, CLIP_HI = 1e-3, 1.0 - 1e-3
 FILES = {"fg": "nerf_hash_model.pt", "bg": "nerf_hash_model_bg.pt"}        # models.py:556-563, train_nerf.py:231-232
+COLORCAL_FILE = "colorcal_model.pt"                                        # models.py:753-760
+COLORCAL_COLS = 6                  # a row of the per-ray sums: COLS of csrc/colorcal_plan.h
 
 
 def plan(nr_rays, max_per_ray=64):
@@ -218,6 +223,87 @@ def nerf_head_join_backward_raw(g_raw, dX2, fd):
     return g_fd
 
 
+# ------------------------------------------------------------------------------------------------- the colour calibration
+def _cc_args(img_idx, colorcal):
+    """the table arguments of the three entries: img_idx [R] int32, I, the fixed image, weight_delta [I, 3], bias [I, 3]"""
+    idx = img_idx if img_idx.dtype == torch.int32 and img_idx.is_contiguous() else img_idx.to(torch.int32).contiguous()
+    return idx, int(colorcal.weight_delta.shape[0]), int(colorcal.idx_with_fixed_calib)
+
+
+@torch.no_grad()
+def colorcal_sigmoid_raw(rs, raw_fm, img_idx, colorcal):
+    """raw_fm [3, M] (the colour head's feature-major output) -> rgb [M, 3] = sigmoid(raw * (1 + weight_delta[img]) + bias[img]),
+    img the image of the sample's ray; rays of the fixed image and of an image outside the tables keep the identity (there, and
+    everywhere with zero tables, the bits of `sigmoid_rows_raw`).  rs: the packed container; colorcal: train_step.Colorcal."""
+    L.require_cuda(raw_fm, img_idx, colorcal.weight_delta)
+    if raw_fm.dim() != 2 or raw_fm.shape[0] != 3 or img_idx.numel() != rs.ray_start_end_idx.shape[0]:
+        raise ValueError("colorcal_sigmoid: raw_fm [3, M] and one image index per ray, got %s and %s" % (tuple(raw_fm.shape), tuple(img_idx.shape)))
+    M = raw_fm.shape[1]
+    idx, I, fixed = _cc_args(img_idx, colorcal)
+    rgb = _per_sample(rs, (M, 3), raw_fm.device)
+    L.call("psdf_colorcal_sigmoid_forward", *rs._ri(), L.c_l(M), L.ptr(_c(raw_fm)), L.ptr(idx), L.c_i(I), L.c_i(fixed),
+           L.ptr(_c(colorcal.weight_delta)), L.ptr(_c(colorcal.bias)), L.ptr(rgb), L.stream())
+    return rgb
+
+
+@torch.no_grad()
+def colorcal_sigmoid_backward_raw(rs, g_rgb, rgb, raw_fm, img_idx, colorcal):
+    """-> (g_raw_fm [3, M] = g_rgb rgb (1 - rgb) w, g_ray [R, 6]: per ray the sums over its samples of g_pre raw (columns 0-2) and
+    of g_pre = g_rgb rgb (1 - rgb) (columns 3-5); zeros for empty rays and rays that keep the identity).  The same inputs give the
+    same bits on every call."""
+    L.require_cuda(g_rgb, rgb, raw_fm)
+    M, R = raw_fm.shape[1], rs.ray_start_end_idx.shape[0]
+    idx, I, fixed = _cc_args(img_idx, colorcal)
+    g_raw_fm = _per_sample(rs, (M, 3), raw_fm.device).view(3, M)       # (zero-filled where the container has unowned slots)
+    g_ray = torch.empty((R, COLORCAL_COLS), dtype=torch.float32, device=raw_fm.device)
+    L.call("psdf_colorcal_sigmoid_backward", *rs._ri(), L.c_l(M), L.ptr(_c(g_rgb)), L.ptr(rgb), L.ptr(_c(raw_fm)), L.ptr(idx), L.c_i(I),
+           L.c_i(fixed), L.ptr(_c(colorcal.weight_delta)), L.ptr(_c(colorcal.bias)), L.ptr(g_raw_fm), L.ptr(g_ray), L.stream())
+    return g_raw_fm, g_ray
+
+
+@torch.no_grad()
+def colorcal_fold_raw(img_idx, colorcal, g_ray_a, g_ray_b=None):
+    """per-ray sums of one branch, or of two (b: the background's, added first) -> (g_weight_delta [I, 3], g_bias [I, 3]): for every
+    image the sum over its rays in ascending ray order; the fixed image's row and the row of an image no ray drew are exactly 0"""
+    L.require_cuda(g_ray_a, g_ray_b)
+    idx, I, fixed = _cc_args(img_idx, colorcal)
+    R = idx.shape[0]
+    if tuple(g_ray_a.shape) != (R, COLORCAL_COLS) or (g_ray_b is not None and g_ray_b.shape != g_ray_a.shape):
+        raise ValueError("colorcal_fold: per-ray sums [R, 6] for %d rays, got %s" % (R, tuple(g_ray_a.shape)))
+    make = torch.zeros if R == 0 else torch.empty        # (the entry writes nothing for an empty batch)
+    g_wd = make((I, 3), dtype=torch.float32, device=g_ray_a.device)
+    g_b = make((I, 3), dtype=torch.float32, device=g_ray_a.device)
+    L.call("psdf_colorcal_fold", L.c_i(R), L.ptr(idx), L.c_i(I), L.c_i(fixed), L.ptr(g_ray_a), L.ptr(g_ray_b), L.ptr(g_wd), L.ptr(g_b),
+           L.stream())
+    return g_wd, g_b
+
+
+class _ColorcalSigmoid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rs, img_idx, colorcal, raw_fm, weight_delta, bias):
+        raw = _c(raw_fm)
+        rgb = colorcal_sigmoid_raw(rs, raw, img_idx, colorcal)
+        ctx.save_for_backward(raw, rgb)
+        ctx.rs, ctx.img_idx, ctx.colorcal = rs, img_idx, colorcal
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g_rgb):
+        raw, rgb = ctx.saved_tensors
+        g_raw_fm, g_ray = colorcal_sigmoid_backward_raw(ctx.rs, g_rgb, rgb, raw, ctx.img_idx, ctx.colorcal)
+        g_wd = g_b = None
+        if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
+            g_wd, g_b = colorcal_fold_raw(ctx.img_idx, ctx.colorcal, g_ray)
+        return None, None, None, g_raw_fm, g_wd, g_b
+
+
+def colorcal_sigmoid(rs, raw_fm, img_idx, colorcal):
+    """-> rgb [M, 3]: Colorcal.calib_RGB_samples_packed + sigmoid of the feature-major raw colours raw_fm [3, M] of the container
+    `rs`, differentiable once w.r.t. raw_fm and the module's two parameters (one launch forward; backward one launch and the
+    fold)"""
+    return _ColorcalSigmoid.apply(rs, img_idx, colorcal, raw_fm, colorcal.weight_delta, colorcal.bias)
+
+
 # ------------------------------------------------------------------------------------------------------------ the network
 class NerfNet(BgNet):
     """NerfHash(in_channels = pos_dim), models.py:425-550: a 24-level lattice of capacity 2^18 over `pos_dim` dimensions with
@@ -242,12 +328,16 @@ class NerfNet(BgNet):
     def window(self, it):
         return self.c2f.window_at(it, self.nr_iters_for_c2f, self.encoding.lattice_values.device)
 
-    def forward(self, pos, dirs, it):
-        """-> (colour [N, 3] after the sigmoid, RAW density [N, 1]: the softplus is the renderer's)"""
+    def forward(self, pos, dirs, it, colorcal=None, img_indices=None, ray_start_end_idx=None):
+        """-> (colour [N, 3] after the sigmoid, RAW density [N, 1]: the softplus is the renderer's).  colorcal (train_step.Colorcal)
+        with the rays' images and the container's ranges: the raw colours are calibrated first (models.py:520-523), in torch
+        operators"""
         with torch.no_grad():
             sh = PermutoSDF.spherical_harmonics(dirs, 4)
         fd = self.mlp_feat_and_density(self.encoding(pos, self.window(it)))
         rgb = self.mlp_rgb(cat_fm([F.gelu(fd[:, 1:65]), sh]))
+        if colorcal is not None:
+            rgb = colorcal.calib_RGB_samples_packed(rgb, img_indices, ray_start_end_idx)
         return torch.sigmoid(rgb), fd[:, 0:1]
 
     @torch.no_grad()
@@ -289,12 +379,23 @@ class NerfTrainer:
     lattices' touched-rows buffers -> AdamW.  No autograd; the loss stays on the device (the step's one host synchronisation
     is the sample count of the march, as in the reference).
     hand_written=False: the same step as an autograd graph over NerfNet.forward, the unfused compositing chain, nerf_composite
-    and `nerf_loss_torch`, from the same batch: what the hand-written step is measured against."""
+    and `nerf_loss_torch`, from the same batch: what the hand-written step is measured against.
 
-    def __init__(self, device, with_mask=False, hand_written=True, hp=None, seed=0, colorcal=None):
+    nr_images: train the reference's per-image colour calibration too (train_nerf.py:52,158-161,169-172): a
+    train_step.Colorcal(nr_images, idx_with_fixed_calib) whose two parameters join the nets' AdamW group (no decay).  By hand the
+    sigmoid of both branches becomes colorcal.hip's fused entry and the per-ray sums of both are folded once per step; as a graph
+    the module goes through NerfNet.forward.  None: no calibration, the step as it was."""
+
+    def __init__(self, device, with_mask=False, hand_written=True, hp=None, seed=0, colorcal=None, nr_images=None,
+                 idx_with_fixed_calib=0):
         if colorcal is not None:
-            raise NotImplementedError("NerfTrainer: the per-image colour calibration of train_nerf.py (Colorcal) is not built; "
-                                      "train without it (colorcal=None)")
+            raise NotImplementedError("NerfTrainer builds its own calibration module: pass nr_images= (and idx_with_fixed_calib=), "
+                                      "not colorcal=")
+        if nr_images is not None:
+            if int(nr_images) < 1:
+                raise ValueError("NerfTrainer: nr_images must be at least 1, got %r" % (nr_images,))
+            if not 0 <= int(idx_with_fixed_calib) < int(nr_images):
+                raise ValueError("NerfTrainer: idx_with_fixed_calib %r is no image of %d" % (idx_with_fixed_calib, int(nr_images)))
         self.hp = hp or HyperParams()
         self.dev = torch.device(device)
         L.require_cuda(torch.empty(0, device=self.dev))
@@ -307,7 +408,10 @@ class NerfTrainer:
         self.nets = [n for n in (self.net, self.net_bg) if n is not None]
         self.sphere = Sphere(0.5, [0, 0, 0])
         self.grid = OccupancyGrid(self.hp.grid_dim, 1.0, [0, 0, 0], device=self.dev)
+        self.colorcal = None if nr_images is None else Colorcal(int(nr_images), int(idx_with_fixed_calib)).to(self.dev)
         self.params = [p for n in self.nets for p in n.parameters() if p.requires_grad]
+        if self.colorcal is not None:
+            self.params += [self.colorcal.weight_delta, self.colorcal.bias]
         self.opt = FusedAdamW([{"params": self.params, "weight_decay": 0.0}], lr=self.hp.lr, betas=(0.9, 0.99), eps=1e-15,
                               weight_decay=0.0)
         self.touched = []
@@ -344,9 +448,9 @@ class NerfTrainer:
         hp = self.hp
         it = self.iter if it is None else it
         parallel.seed_generators(parallel.step_seed(self._seed, 0, it, world=1), self.dev)
-        o, d, gt, gt_mask, _ = PermutoSDF.random_rays_from_reel(reel, hp.nr_rays)
+        o, d, gt, gt_mask, img_idx = PermutoSDF.random_rays_from_reel(reel, hp.nr_rays)
         hit, fg, bg = self.sample(o, d, True)
-        return SimpleNamespace(gt=gt, gt_mask=gt_mask, hit=hit, fg=fg, bg=bg, R=o.shape[0], n_fg=fg.samples_pos.shape[0])
+        return SimpleNamespace(gt=gt, gt_mask=gt_mask, hit=hit, fg=fg, bg=bg, R=o.shape[0], n_fg=fg.samples_pos.shape[0], img_idx=img_idx)
 
     @torch.no_grad()
     def sample(self, o, d, jitter):
@@ -372,9 +476,10 @@ class NerfTrainer:
         return views
 
     @staticmethod
-    def _branch_forward(net, pts, dirs, it, train=True):
+    def _branch_forward(net, pts, dirs, it, train=True, calib=None):
         """lattice -> density + feature net -> [gelu(features); SH4(dir)] (one launch) -> colour head -> sigmoid.  train=False
-        (rendering): the lattice rows read are not marked for the optimiser"""
+        (rendering): the lattice rows read are not marked for the optimiser.  calib = (container, img_idx, Colorcal): the
+        calibrated sigmoid of colorcal.hip in the plain one's place"""
         win = net.window(it).contiguous()
         feat = enc_forward(net.encoding, pts, win, train)
         net1 = d1, _, w1, b1 = net_params(net.mlp_feat_and_density)
@@ -383,20 +488,28 @@ class NerfTrainer:
             fd = mlp_forward_raw(d1, feat, pack_params(d1, w1, b1))
         x2 = nerf_head_join_raw(fd, PermutoSDF.spherical_harmonics(dirs, 4))  # [80, M]
         net2 = d2, _, w2, b2 = net_params(net.mlp_rgb)
-        rgb = sigmoid_rows_raw(mlp_forward_raw(d2, x2, pack_params(d2, w2, b2)))   # [M, 3]
-        return SimpleNamespace(net=net, pts=pts, win=win, feat=feat, fd=fd, x2=x2, net1=net1, net2=net2, rgb=rgb, raw_den=fd[0])
+        raw_fm = mlp_forward_raw(d2, x2, pack_params(d2, w2, b2))                 # [3, M]
+        rgb = sigmoid_rows_raw(raw_fm) if calib is None else colorcal_sigmoid_raw(calib[0], raw_fm, calib[1], calib[2])   # [M, 3]
+        return SimpleNamespace(net=net, pts=pts, win=win, feat=feat, fd=fd, x2=x2, net1=net1, net2=net2, rgb=rgb, raw_den=fd[0],
+                               calib=calib, raw_fm=raw_fm if calib is not None else None)
 
     @staticmethod
     def _branch_backward(B, g_raw, g_rgb, into1, into2):
         """the net's gradients into the zero-filled views into1 (density + feature net) / into2 (colour head), the lattice's
-        into its touched-rows buffer"""
+        into its touched-rows buffer -> the calibration's per-ray sums [R, 6] (None without calibration)"""
         (d1, l1, w1, b1), (d2, l2, w2, b2) = B.net1, B.net2
-        dX2, dW2, db2 = mlp_backward_raw(d2, B.x2, w2, b2, sigmoid_rows_backward_raw(g_rgb, B.rgb), need_dx=True, into=into2)
+        g_ray = None
+        if B.calib is None:
+            g_raw_fm = sigmoid_rows_backward_raw(g_rgb, B.rgb)
+        else:
+            g_raw_fm, g_ray = colorcal_sigmoid_backward_raw(B.calib[0], g_rgb, B.rgb, B.raw_fm, B.calib[1], B.calib[2])
+        dX2, dW2, db2 = mlp_backward_raw(d2, B.x2, w2, b2, g_raw_fm, need_dx=True, into=into2)
         set_grads(l2, dW2, db2)
         g_fd = nerf_head_join_backward_raw(g_raw, dX2, B.fd)                  # [65, M]
         dX, dW1, db1 = mlp_backward_raw(d1, B.feat, w1, b1, g_fd, need_dx=True, into=into1)
         set_grads(l1, dW1, db1)
         enc_backward(B.net.encoding, B.pts, B.win, dX)
+        return g_ray
 
     # ---- the two forms of a step
     @torch.no_grad()
@@ -407,8 +520,10 @@ class NerfTrainer:
             for l, dW, db in zip(m.layers, dWs, dbs):
                 l.weight.grad, l.bias.grad = dW, db
         fg = ws = None
+        cc = self.colorcal
+        g_ray_fg = g_ray_bg = None
         if b.n_fg:
-            fg = self._branch_forward(self.net, b.fg.samples_pos, b.fg.samples_dirs, it)
+            fg = self._branch_forward(self.net, b.fg.samples_pos, b.fg.samples_dirs, it, calib=None if cc is None else (b.fg, b.img_idx, cc))
             pred_fg, ws, bgT = nerf_render_raw(b.fg, fg.raw_den, fg.rgb, want_weights_sum=self.with_mask, want_bg=not self.with_mask)
         else:
             pred_fg = torch.zeros(b.R, 3, device=dev)
@@ -419,22 +534,30 @@ class NerfTrainer:
             loss, _, g_pred, g_ws = nerf_loss_raw(pred_fg, b.gt, b.hit, ws, b.gt_mask, hp.mask_weight, workspace=work, terms=self.last_terms)
             g_bgT = None
         else:
-            bg = self._branch_forward(self.net_bg, b.bg.samples_pos_4d, b.bg.samples_dirs, it)
+            bg = self._branch_forward(self.net_bg, b.bg.samples_pos_4d, b.bg.samples_dirs, it, calib=None if cc is None else (b.bg, b.img_idx, cc))
             # the background's render and pred = pred_fg + bgT * pred_bg: one launch per direction
             _, pred = nerf_composite_forward_raw(b.bg, bg.raw_den, bg.rgb, pred_fg, bgT)
             loss, _, g_pred, g_ws = nerf_loss_raw(pred, b.gt, b.hit, workspace=work, terms=self.last_terms)
             g_rawb, g_rgbb, g_bgT = nerf_composite_backward_raw(b.bg, hp.nr_samples_bg, g_pred, bg.raw_den, bg.rgb, bgT)
-            self._branch_backward(bg, g_rawb, g_rgbb, arena[2], arena[3])
+            g_ray_bg = self._branch_backward(bg, g_rawb, g_rgbb, arena[2], arena[3])
         if fg is not None:
             g_raw, g_rgb = nerf_render_backward_raw(b.fg, hp.max_nr_samples_per_ray, g_pred, g_ws, g_bgT, fg.raw_den, fg.rgb)
-            self._branch_backward(fg, g_raw, g_rgb, arena[0], arena[1])
+            g_ray_fg = self._branch_backward(fg, g_raw, g_rgb, arena[0], arena[1])
+        if cc is not None:      # one fold per step, the background's sums first; one branch alone; no samples at all: zeros
+            if g_ray_fg is None and g_ray_bg is None:
+                cc.weight_delta.grad, cc.bias.grad = torch.zeros_like(cc.weight_delta), torch.zeros_like(cc.bias)
+            elif g_ray_fg is None or g_ray_bg is None:
+                cc.weight_delta.grad, cc.bias.grad = colorcal_fold_raw(b.img_idx, cc, g_ray_bg if g_ray_fg is None else g_ray_fg)
+            else:
+                cc.weight_delta.grad, cc.bias.grad = colorcal_fold_raw(b.img_idx, cc, g_ray_fg, g_ray_bg)
         return loss
 
     def _step_autograd(self, b, it):
         hp, dev = self.hp, self.dev
         ws = None
+        cc = self.colorcal
         if b.n_fg:
-            rgb, raw = self.net(b.fg.samples_pos, b.fg.samples_dirs, it)
+            rgb, raw = self.net(b.fg.samples_pos, b.fg.samples_dirs, it, cc, b.img_idx, b.fg.ray_start_end_idx)
             alpha, one_minus = nerf_alpha(raw, b.fg.samples_dt)
             T, bgT = _Cumprod.apply(b.fg, one_minus)
             w = (alpha * T).view(-1, 1)
@@ -445,7 +568,7 @@ class NerfTrainer:
         if self.with_mask:
             loss, terms = nerf_loss_torch(pred, b.gt, b.hit, ws, b.gt_mask, hp.mask_weight)
         else:
-            rgb_b, raw_b = self.net_bg(b.bg.samples_pos_4d, b.bg.samples_dirs, it)
+            rgb_b, raw_b = self.net_bg(b.bg.samples_pos_4d, b.bg.samples_dirs, it, cc, b.img_idx, b.bg.ray_start_end_idx)
             pred = nerf_composite(b.bg, hp.nr_samples_bg, raw_b, rgb_b, pred, bgT.view(-1, 1))
             loss, terms = nerf_loss_torch(pred, b.gt, b.hit)
         self.last_terms = terms
@@ -491,10 +614,12 @@ class NerfTrainer:
         from . import checkpoint
         os.makedirs(folder, exist_ok=True)
         torch.save(checkpoint.to_reference_keys("bg", self.net.state_dict()), os.path.join(folder, FILES["fg"]))
-        checkpoint.save(folder, bg=self.net_bg, grid=self.grid)
+        checkpoint.save(folder, bg=self.net_bg, grid=self.grid, colorcal=self.colorcal)      # colorcal_model.pt: weight_delta, bias
 
     def load_checkpoint(self, folder):
         from . import checkpoint
         sd = torch.load(os.path.join(folder, FILES["fg"]), map_location=self.dev)
         self.net.load_state_dict(checkpoint.from_reference_keys("bg", sd))
-        checkpoint.load(folder, bg=self.net_bg, grid=self.grid, map_location=self.dev)
+        # a checkpoint of a run without calibration loads into a calibrated trainer: the tables stay as they are (zero when new)
+        cc = self.colorcal if os.path.exists(os.path.join(folder, COLORCAL_FILE)) else None
+        checkpoint.load(folder, bg=self.net_bg, grid=self.grid, colorcal=cc, map_location=self.dev)

@@ -24,7 +24,8 @@ under the rendering weights, not normalised by the weight sum (divide by `weight
 
 Rendering reads a run and leaves it as it was: parameters, gradients, optimiser moments, `iter`, the grid's values and pool
 size, the lattices' touched-rows buffers and the device's random state are not written.  No colour calibration (the reference
-renders views with model_colorcal=None, train_nerf.py:107), no image files.  CPU tensors raise PsdfError: there is no CPU path.
+renders views with model_colorcal=None, train_nerf.py:107): of a run trained with `NerfTrainer(nr_images=...)` a view carries
+the calibration of the fixed image, the identity.  No image files.  CPU tensors raise PsdfError: there is no CPU path.
 """
 import dataclasses
 import os
