@@ -948,6 +948,52 @@ int psdf_box_trace_resolve(int nr_rays, int stride, const float* origins, const 
     sdf_end, const float* gradients, const uint8_t* no_hit, float coverage_thresh, const float* rot_cam_world, int H, int W,
     int64_t pixel_first, float* normals_img, float* normals_cam_img, float* weights_sum_img, float* depth_img, void* stream);
 
+/* ---- sdf_slice.hip ---- */
+/* Cross-sections of an SDF: the layer of points of create_sdf_isolines, its colour map with iso-bands, and the depth test of
+   the layer against a rendered view.  The plane comes as HOST values: axes, 9 floats of a row-major 3 x 3 matrix whose COLUMNS
+   are the plane's axes (the reference's cam.cam_axes()), the layer depth z along the third axis and the half width of the
+   layer (extent_scale; 1 is the reference's [-1, 1)).  The box comes as the host triples translation and half = sizes / 2 of
+   psdf_box_trace_step.  Points are rows of `stride` floats, stride 3, or 4 with the time in column 3 (time: DEVICE pointer to
+   one float, may be NULL with stride 3); flags are bytes.  The colour arguments are: table [K, 3] on the DEVICE, 2 <= K <=
+   65536; base_map, 4 HOST floats (in_lo, in_hi, out_lo, scale) of a map_range whose scale = (out_hi - out_lo) / (in_hi - in_lo)
+   the caller computed in float64 and rounded; nr_lines <= 32 bands as the HOST arrays band_lo, band_hi [nr_lines] and band_rgb
+   [nr_lines, 3] (may be NULL with nr_lines = 0).  The colour of a value s is 0 for a NaN, else table(base_map(s)) -- overwritten
+   by band_rgb[i] of the LAST i with s > band_lo[i] && s < band_hi[i] (float32, both strict).  csrc/sdf_slice.hip states the
+   evaluation order of table() and of the rotation, both restated and unpinned.  The entries allocate nothing and never
+   synchronise; a count of 0 returns 0 without a launch; -1 for a negative count, a stride other than 3 or 4, nr_lines outside
+   [0, 32], K outside [2, 65536], an extent < 1, a range outside the layer or the frame, or a NULL required pointer; -2 for
+   S S >= 2^31 or H W >= 2^31. */
+/* replaces: the layer of create_sdf_isolines (permuto_sdf_py/experiments/visualization/visualize_sdf_isolines.py:69-92, 96-101;
+   render_from_frame.py:71-166 and sample_sdf_in_layer of permuto_sdf_py/utils/sdf_utils.py build the same layer) and
+   AABB.check_point_inside_primitive (permuto_sdf_py/utils/aabb.py:28-42) on it, for the cells [first, first + count) of an
+   S x S layer; cell k has row k / S (y) and column k % S (x).  pts [count, stride] <- the rotated cell (float32 lattice, float64
+   rotation rounded once), column 3 <- time[0] with stride 4; skip [count] <- !(strictly inside the box) */
+int psdf_slice_points(int S, int64_t first, int count, int stride, const float* axes, float z, float extent_scale, const float*
+    translation, const float* half, const float* time, float* pts, uint8_t* skip, void* stream);
+/* replaces: the colour map and the 15 masked assignments of visualize_sdf_isolines.py:111-138 (map_range_tensor,
+   permuto_sdf_py/utils/common_utils.py:150-154; the defaults of src/NGPGui.cxx:22-25) and remove_marked_vertices (:153-156), for
+   the same cells: sdf, skip [count] -> at cell first + i of the planes rgb [3, S, S] <- the colour, sdf_img [1, S, S] <- sdf,
+   inside_img [1, S, S] <- 1; a skipped cell gets 0 in all three.  Every cell of the range is written once, nothing outside it */
+int psdf_slice_colorize(int S, int64_t first, int count, const float* sdf, const uint8_t* skip, const float* table, int K, const
+    float* base_map, int nr_lines, const float* band_lo, const float* band_hi, const float* band_rgb, float* rgb, float*
+    sdf_img, float* inside_img, void* stream);
+/* replaces: the viewer's depth test of the layer against the scene (Scene.show, visualize_sdf_isolines.py:158-162, and
+   render_easypbr_from_frame :171-203), first half, for the rays [pixel_first, pixel_first + nr_rays) of an H x W frame (origins,
+   dirs [nr_rays, 3] as from psdf_frame_rays).  With n the third axis: t = dot(n, z n - o) / dot(n, d), p = o + t d, all float32.
+   A ray takes part iff dot(n, d) != 0, t > 0, dot(a0, p) and dot(a1, p) lie in [-extent, extent), p is strictly inside the
+   box, and weights_sum_img[pixel] == 0 || t < depth_img[pixel].  pts [nr_rays, stride] <- p (the origin for a ray that does
+   not take part), column 3 <- time[0]; skip [nr_rays] <- !takes part; t [nr_rays] <- t (0 for a ray that does not) */
+int psdf_slice_cut_begin(int nr_rays, int stride, const float* axes, float z, float extent, const float* translation, const
+    float* half, const float* origins, const float* dirs, const float* time, int H, int W, int64_t pixel_first, const float*
+    weights_sum_img, const float* depth_img, float* pts, uint8_t* skip, float* t, void* stream);
+/* replaces: the second half of the same (visualize_sdf_isolines.py:158-162 with the colours of :111-138), after the network:
+   for a ray with skip == 0, rgb_img [3, H, W] <- the colour of sdf[ray], depth_img <- t[ray], weights_sum_img <- 1,
+   slice_mask_img [1, H, W] <- 1, in place at pixel pixel_first + ray; for any other ray slice_mask_img <- 0 and the other planes
+   keep their bits */
+int psdf_slice_cut_resolve(int nr_rays, const float* sdf, const uint8_t* skip, const float* t, const float* table, int K, const
+    float* base_map, int nr_lines, const float* band_lo, const float* band_hi, const float* band_rgb, int H, int W, int64_t
+    pixel_first, float* rgb_img, float* depth_img, float* weights_sum_img, float* slice_mask_img, void* stream);
+
 /* ---- colorcal.hip ---- */
 /* Per-image colour calibration of NeRF training (permuto_sdf_py/train_nerf.py:52,158-161; Colorcal, models.py:678-729), applied
    to the raw colours of a packed container before the sigmoid (models.py:520-523).  Ray-index arguments as

@@ -10,9 +10,12 @@ from . import sdf_fit
 from . import nerf_train
 from . import nerf_view
 from . import box_trace
+from . import sdf_slice
 from .box_trace import Box, BoxPlayer, BoxTracedFrame, BoxTracer, render_box_traced
+from .sdf_slice import PUBU, IsoStyle, SliceImage, SlicePlane, SlicedFrame, cut_slice_into, render_slice
 from .encoding import PermutoEncoding, Coarse2Fine
 from .mlp import FusedMLP, LipshitzMLP
 
 __all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval", "render", "sdf_fit", "nerf_train", "nerf_view",
-           "box_trace", "Box", "BoxTracer", "BoxPlayer", "BoxTracedFrame", "render_box_traced"]
+           "box_trace", "Box", "BoxTracer", "BoxPlayer", "BoxTracedFrame", "render_box_traced",
+           "sdf_slice", "SlicePlane", "IsoStyle", "PUBU", "SliceImage", "SlicedFrame", "render_slice", "cut_slice_into"]

@@ -12,7 +12,10 @@ results appended to Python lists, concatenated, and transposed into images (lin2
   * `FrameRenderer(trainer).render_traced(frame)` -> `TracedFrame`: rgb, normals, normals_cam, weights_sum, depth of the
                                               surface a sphere trace finds (below);
   * `FrameRenderer.render_views(frames)`      -> [N, 3, H, W], what `image_eval.evaluate_views` takes (`mode="traced"`: the
-                                              sphere-traced colours).
+                                              sphere-traced colours);
+  * `FrameRenderer.slice(plane)`              -> `sdf_slice.SliceImage`: the isolines of the SDF net on a layer, inside the cube of
+                                              the occupancy grid (sdf_slice.py; `sdf_slice.cut_slice_into` cuts such a layer into
+                                              the planes of a traced frame).
 
 A frame is cut into chunks by `psdf_frame_plan`: the largest multiple of 64 rays whose uniform samples cannot overflow the
 march's sample pool (32 768 rays at the reference's pool and 64 samples per ray: 59 chunks for 1600 x 1200 instead of 640).
@@ -361,6 +364,20 @@ class FrameRenderer:
             self._traced_chunk(frame, first, count, tracer, (nr_sphere_traces, sdf_multiplier, sdf_converged_tresh), it, out, rot,
                                work)
         return out
+
+    def box(self):
+        """the axis-aligned box of the scene, as a box_trace.Box: the cube of the occupancy grid"""
+        from .box_trace import Box
+        g = self.trainer.grid
+        return Box([g.m_grid_extent] * 3, g.m_grid_translation)
+
+    def slice(self, plane, size=500, box=None, **kw):
+        """-> sdf_slice.SliceImage: the isolines of the SDF net on `plane` (a sdf_slice.SlicePlane), as
+        render_from_frame.py:71-166 draws them; box: default `self.box()`; kw: sdf_slice.render_slice's (`it` None: the lattice
+        window fully open)"""
+        from .sdf_slice import render_slice
+        self.trainer._params_ready()
+        return render_slice(self.trainer.sdf, plane, self.box() if box is None else box, size, **kw)
 
     def render_views(self, frames, mode="volumetric", **kwargs):
         """-> [N, 3, H, W] float32: the rgb of every frame (all of one size), ready for image_eval.evaluate_views; mode

@@ -404,11 +404,29 @@ class SdfFitter:
         from .box_trace import BoxTracer
         return BoxTracer(self.net.encoding, self.net.mlp_sdf, self.box() if box is None else box, self.net.window(self.iter))
 
-    def render(self, frame, t=None, box=None, **kw):
-        """-> box_trace.BoxTracedFrame: the fitted field as `frame` sees it (a 4-D one at time t); kw: render_box_traced's"""
+    def render(self, frame, t=None, box=None, slice=None, slice_style=None, **kw):
+        """-> box_trace.BoxTracedFrame: the fitted field as `frame` sees it (a 4-D one at time t); kw: render_box_traced's.
+        slice: a sdf_slice.SlicePlane to cut into the view -> sdf_slice.SlicedFrame instead: rgb = (normal + 1) / 2 as
+        vis_4d_sdf.py:108 maps it, with the layer's isolines where the layer is in front of the surface or there is none; the
+        depth and weights_sum planes of its `base` are cut in place"""
         from .box_trace import render_box_traced
         kw.setdefault("it", self.iter)
-        return render_box_traced(self.net, self.box() if box is None else box, frame, time_val=t, **kw)
+        box = self.box() if box is None else box
+        out = render_box_traced(self.net, box, frame, time_val=t, **kw)
+        if slice is None:
+            return out
+        from .sdf_slice import IsoStyle, SlicedFrame, cut_slice_into
+        rgb = (out.normals + 1.0) * 0.5
+        chunk = {"max_rays_per_chunk": kw["max_rays_per_chunk"]} if "max_rays_per_chunk" in kw else {}
+        mask = cut_slice_into(self.net, slice, box, frame, rgb, out.depth, out.weights_sum, IsoStyle() if slice_style is None else
+                              slice_style, it=kw["it"], time_val=t, **chunk)
+        return SlicedFrame(base=out, rgb=rgb, depth=out.depth, weights_sum=out.weights_sum, slice_mask=mask)
+
+    def slice(self, plane, size=500, t=None, box=None, **kw):
+        """-> sdf_slice.SliceImage: the isolines of the fitted field on `plane` (a 4-D one at time t); kw: render_slice's"""
+        from .sdf_slice import render_slice
+        kw.setdefault("it", self.iter)
+        return render_slice(self.net, plane, self.box() if box is None else box, size, time_val=t, **kw)
 
     # ---- checkpoints: the reference's sdf_model.pt (models.py:296-307) through checkpoint.py
     def save_checkpoint(self, folder):
