@@ -611,6 +611,8 @@ class NerfTrainer:
 
     # ---- checkpoints: the reference's nerf_hash_model.pt / nerf_hash_model_bg.pt and the two grid tensors (train_nerf.py:230-238)
     def save_checkpoint(self, folder):
+        # (one process, no collectives: no parameter all-gather is ever in flight here, unlike train_step.Trainer.save_checkpoint,
+        # which waits for its own first; a data-parallel step added to this trainer has to bring that wait along)
         from . import checkpoint
         os.makedirs(folder, exist_ok=True)
         torch.save(checkpoint.to_reference_keys("bg", self.net.state_dict()), os.path.join(folder, FILES["fg"]))

@@ -122,13 +122,26 @@ class Loopback:
     correctness of the SCHEDULE: a collective is enqueued on a side stream that first waits for what the caller's current stream
     has enqueued so far, runs for a while (`delay_cycles` of device sleep, so that a consumer that forgot to wait reads stale
     data), and `wait()` makes the caller's current stream wait for it.  The 'sum over `world` ranks' of identical replicas is
-    t * world.  Activate with `parallel.set_loopback(Loopback(world=2))`; world_size() then reports `world`."""
+    t * world.  Activate with `parallel.set_loopback(Loopback(world=2))`; world_size() then reports `world`.
 
-    def __init__(self, world=2, delay_cycles=2_000_000, serialize=False):
+    hold=True is the DETERMINISTIC form of the two collectives a training step leaves in flight across other work -- the
+    parameter all-gather (`gather_params`) and the lattices' early reductions (`all_reduce`, the path of
+    ShardedUpdate.reduce_scatter).  The timed form restores the buffer after `delay_cycles` whether or not anybody waited: a
+    reader that forgot to wait is caught only if it runs inside that window, and a test that looks at the values with a host
+    sync closes the window itself.  Under hold the buffer is set to NaN at launch (on the caller's stream) and STAYS NaN
+    until `wait()`, which enqueues the result on the stream that is current when it is called: a reader that did not wait
+    sees NaN for any `delay_cycles` and any host timing, a kernel that still adds to a gradient after its reduction was
+    started loses its contribution every time, and a collective nobody waits for leaves NaN behind.  `reduce_scatter` and
+    `all_gather` (the small dense buckets of GradientBuckets, launched from step() once the whole backward is enqueued and
+    finished a few lines later) stay timed under hold.  `serialize=True` keeps its meaning: waited for at once, so restored at
+    once."""
+
+    def __init__(self, world=2, delay_cycles=2_000_000, serialize=False, hold=False):
         self.world, self.delay = int(world), int(delay_cycles)
         self.stream = torch.cuda.Stream()
         self.launched = []      # (kind, numel) log for the tests
         self.serialize = bool(serialize)    # every collective is waited for at once: the race-free reference schedule
+        self.hold = bool(hold)              # gather_params / all_reduce keep NaN in the buffer until wait()
 
     class _Work:
         def __init__(self, ev):
@@ -136,6 +149,45 @@ class Loopback:
 
         def wait(self):
             torch.cuda.current_stream().wait_event(self.ev)
+
+    class _HeldWork:
+        """hold mode: the buffer holds NaN until wait() writes `keep * scale` into it on the CURRENT stream (once)"""
+
+        def __init__(self, ev, buf, keep, scale):
+            self.ev, self.buf, self.keep, self.scale = ev, buf, keep, scale
+
+        def wait(self):
+            cur = torch.cuda.current_stream()
+            cur.wait_event(self.ev)
+            keep, self.keep = self.keep, None
+            if keep is None:
+                return
+            keep.record_stream(cur)         # (allocated on the launching stream, last used on this one)
+            with torch.no_grad():
+                if self.scale == 1:
+                    self.buf.copy_(keep)
+                else:
+                    torch.mul(keep, self.scale, out=self.buf)
+
+    def _held(self, buf, scale, kind):
+        """launch of a held collective on `buf`: snapshot it and fill it with NaN, hand out the work.  Both are enqueued on the
+        CALLER's stream, i.e. exactly at the launch: on the side stream (which only starts behind the caller's stream, it does
+        not hold it back) the fill would race with whatever the caller enqueues next -- a read right behind the launch could
+        still see the old bytes, an add right behind it could still get into the snapshot.  The side stream keeps what makes the
+        collective asynchronous: it takes `delay_cycles`, and wait() makes the waiting stream sit them out."""
+        with torch.no_grad():
+            keep = buf.clone()
+            buf.fill_(float("nan"))
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            torch.cuda._sleep(self.delay)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self.launched.append((kind, buf.numel()))
+        work = Loopback._HeldWork(ev, buf, keep, scale)
+        if self.serialize:
+            work.wait()
+        return work
 
     def _run(self, fn, kind, numel):
         self.stream.wait_stream(torch.cuda.current_stream())
@@ -152,7 +204,10 @@ class Loopback:
     def gather_params(self, flat):
         """the parameter all-gather of the sharded update: identical virtual replicas already hold every owner's bytes, so the
         result is `flat` itself -- but WHILE the collective runs the buffer holds NaN (a real all-gather overwrites the ranges of
-        the other owners while it runs): a reader that did not wait sees them"""
+        the other owners while it runs): a reader that did not wait sees them -- if it runs before the sleep is over, or, under
+        `hold`, whenever it runs"""
+        if self.hold:
+            return self._held(flat, 1, "all_gather_params")
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             keep = flat.clone()
@@ -168,6 +223,8 @@ class Loopback:
         return Loopback._Work(ev)
 
     def all_reduce(self, t, op="sum"):
+        if self.hold and op == "sum":       # the sum of what the buffer held AT LAUNCH; NaN in it until wait()
+            return self._held(t, self.world, "all_reduce")
         return self._run((lambda: t.mul_(self.world)) if op == "sum" else (lambda: None), "all_reduce", t.numel())
 
     def reduce_scatter(self, shard, flat, rank=0):

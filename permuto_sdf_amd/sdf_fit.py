@@ -430,6 +430,8 @@ class SdfFitter:
 
     # ---- checkpoints: the reference's sdf_model.pt (models.py:296-307) through checkpoint.py
     def save_checkpoint(self, folder):
+        # (one process, no collectives: no parameter all-gather is ever in flight here, unlike train_step.Trainer.save_checkpoint,
+        # which waits for its own first; a data-parallel step added to this fitter has to bring that wait along)
         from . import checkpoint
         checkpoint.save(folder, sdf=self.net)
 

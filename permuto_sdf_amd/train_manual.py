@@ -414,7 +414,9 @@ class ManualTrainer(Trainer):
             if st.bg is None:              # (a sampler replaced from outside that left the hook alone)
                 st.bg = self._bg_forward(bgs, st.calib)
         st.n_fg = fgs.samples_pos.shape[0]
-        self._params_ready(0)              # the SDF lattice's parameters, before anything below reads them (data parallel)
+        # the SDF lattice's parameters, before anything below reads them (data parallel): a no-op after `Trainer._samples`, which
+        # waits before its first sdf_only; it counts for a sampler replaced from outside
+        self._params_ready(0)
         dims, _, ws, bs = net_params(sdfn.mlp_sdf)
         # the SDF network as the step's three evaluations share it; win: this iteration's lattice window, gb: its gradient buffer
         st.net = SimpleNamespace(dims=dims, ws=ws, bs=bs, win=sdfn.window(it).contiguous(), packed=pack_params(dims, ws, bs),

@@ -433,6 +433,7 @@ class Trainer:
     # ---- checkpoints in the reference's file layout (permuto_sdf_utils.py:222-237)
     def save_checkpoint(self, folder):
         from . import checkpoint
+        self._params_ready()      # a reader of all three tables: their all-gathers of the last step may still be in flight
         checkpoint.save(folder, sdf=self.sdf, rgb=self.rgb, bg=self.bg, grid=self.grid, colorcal=self.colorcal)
 
     def load_checkpoint(self, folder):
@@ -486,6 +487,9 @@ class Trainer:
         # (combine_count_kernel: n <= 1 ? 0 : n + nr_imp), so the later counts are host arithmetic
         if between is not None:
             between(bg)
+        # the SDF lattice is read below, by both sdf_only calls (data parallel: its all-gather of the previous step); enqueued
+        # behind what `between` enqueued and before the host waits, so the wait costs no host time
+        self._params_ready(0)
         b["event"].synchronize()
         counts = b["counts"]
         n_known, nonempty = int(counts.sum()), int((counts > 0).sum())
@@ -568,7 +572,15 @@ class Trainer:
 
     def _params_ready(self, k=None):
         """make the current stream wait for the all-gather of lattice k's parameters (all of them: k = None) that the previous
-        step left in flight; no-op when nothing is pending.  Everything that READS lattice parameters calls this first."""
+        step left in flight; no-op when nothing is pending (always, on one GPU).  Two rules hold the schedule together:
+          * readers: everything that READS a lattice's parameters calls this first -- inside a step where the table is first
+            read (`_samples` before its first sdf_only, the branches' forwards, the grid refresh), outside a step before anything
+            is read at all (save_checkpoint, render.FrameRenderer; `sync_parameters` for everybody else);
+          * the writer: no gather outlives the next optimiser step.  step() calls this for every table right before `opt.step`,
+            which writes them: a step that never read a table (no foreground samples: the colour lattice) has not waited for
+            its gather, and that the gather is over by then -- because the collectives share one communicator stream, and this
+            step's reduce-scatters, which the main stream has waited for, were enqueued behind it -- is nothing the code
+            should have to know."""
         if not self._pending_gather:
             return
         for key in ([k] if k is not None else list(self._pending_gather)):
@@ -717,6 +729,7 @@ class Trainer:
             self._dp_started = {}
             if self.capture_grads is not None:      # tests: the lattice gradients AFTER the sum over the ranks
                 self.capture_grads["lattices_reduced"] = [tr.grad.clone() for tr in self.touched]
+        self._params_ready()      # the optimiser WRITES the tables: no all-gather of the last step outlives this point
         self.opt.step(grad_scale=1.0 / parallel.world_size(), owned=owned or None)
         if owned:
             # the owners' bytes to everybody, in the order the next step reads the tables (background first: its forward is
