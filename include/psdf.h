@@ -1082,6 +1082,35 @@ int psdf_frame_composite_nerf(int nr_rays, const int* start_end, int equal, int 
     raw_density, const float* dt, const float* rgb, const float* transmittance, int H, int W, int64_t pixel_first, float*
     rgb_img, float* rgb_bg_img, void* stream);
 
+/* ---- mesh_color.hip ---- */
+/* Per-vertex colour of an extracted surface: the glue around the colour network (RgbNet, models.py:310-391) when it is asked
+   about the n vertices of a mesh.  x_fm [C, n] is the network's feature-major input, rows [colour encoding | 25 SH values of
+   degree 5 of the view direction | unit normal | g geometry features]; the colour encoding's rows are written by
+   psdf_encode_forward into the same buffer.  The entries allocate nothing and never synchronise; n == 0 returns 0 before any
+   pointer is looked at; -1: n < 0 or an argument below; -2: n > 2^31 - 1 vertices in one launch, C > 2^16. */
+/* host only: the rows of x_fm and the chunks of a call (csrc/mesh_color_plan.h) -> out [PSDF_MESH_COLOR_PLAN_FIELDS] int64: 0
+   c_enc, the row at which the SH block starts (= rgb_enc_width); 1 c_sh, at which the normal starts; 2 c_normal, at which the
+   geometry features start; 3 c_geom, one past them; 4 C = c_geom; 5 the number of chunks of n vertices in chunks of `chunk`; 6 the
+   vertices of the last chunk (0, 0 for n == 0).  -1: rgb_enc_width < 1, g < 0, C != mlp_in (the width the colour MLP takes),
+   n < 0, chunk < 1, out NULL; -2: C > 2^16, chunk > 2^31 - 1 */
+#define PSDF_MESH_COLOR_PLAN_FIELDS 7
+int psdf_mesh_color_plan(int rgb_enc_width, int g, int mlp_in, int64_t n, int64_t chunk, int64_t* out);
+/* replaces, for vertices: PermutoSDF.spherical_harmonics + F.normalize + the torch.cat (with its transposes) of RgbNet.forward
+   (models.py:352-372).  points [n, 3]; gradients [n, 3] the SDF gradients; y_fm [1 + g, n] the SDF net's feature-major output
+   (row 0, the SDF, is not read).  Per vertex: nrm = G / max(|G|, 1e-12) (the bits of psdf_normalize3); view direction d = -nrm
+   (mode 0: the surface seen head-on from outside) or (p - eye) / max(|p - eye|, 1e-12) (mode 1; eye: device pointer to 3
+   floats; points is read in this mode only); rows [sh_row, sh_row + 25) of x_fm <- the SH values of d (the bits of
+   psdf_spherical_harmonics), rows [sh_row + 25, sh_row + 28) <- nrm, rows [sh_row + 28, sh_row + 28 + g) <- rows 1 .. g of
+   y_fm; dirs [n, 3] or NULL <- d; normals [n, 3] or NULL <- nrm.  Rows [0, sh_row) are not touched.  A zero gradient gives
+   nrm = 0 and d = 0 (no special case).  -1: g < 0, sh_row < 0, a mode other than 0 and 1, sh_row + 28 + g != C, a NULL pointer
+   that is read or x_fm NULL. */
+int psdf_mesh_color_inputs(int64_t n, const float* points, const float* gradients, const float* y_fm, int g, int mode, const
+    float* eye, float* x_fm, int C, int sh_row, float* dirs, float* normals, void* stream);
+/* replaces, for vertices: torch.sigmoid of RgbNet.forward (models.py:391) and the 8-bit conversion of the views (image_eval.to_u8) on the
+   colour head's feature-major output raw_fm [3, n] -> rgb [n, 3] or NULL <- 1 / (1 + expf(-raw)) (the bits of
+   psdf_sigmoid_rows); rgb_u8 [n, 3] uint8 or NULL <- clamp(rint(rgb * 255), 0, 255), ties to even.  -1: raw_fm NULL. */
+int psdf_mesh_color_finish(int64_t n, const float* raw_fm, float* rgb, uint8_t* rgb_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,8 @@ from . import nerf_train
 from . import nerf_view
 from . import box_trace
 from . import sdf_slice
+from . import mesh_color
+from .mesh_color import MeshColorizer, VertexColors
 from .box_trace import Box, BoxPlayer, BoxTracedFrame, BoxTracer, render_box_traced
 from .sdf_slice import PUBU, IsoStyle, SliceImage, SlicePlane, SlicedFrame, cut_slice_into, render_slice
 from .encoding import PermutoEncoding, Coarse2Fine
@@ -18,4 +20,5 @@ from .mlp import FusedMLP, LipshitzMLP
 
 __all__ = ["PermutoEncoding", "Coarse2Fine", "FusedMLP", "LipshitzMLP", "image_eval", "render", "sdf_fit", "nerf_train", "nerf_view",
            "box_trace", "Box", "BoxTracer", "BoxPlayer", "BoxTracedFrame", "render_box_traced",
-           "sdf_slice", "SlicePlane", "IsoStyle", "PUBU", "SliceImage", "SlicedFrame", "render_slice", "cut_slice_into"]
+           "sdf_slice", "SlicePlane", "IsoStyle", "PUBU", "SliceImage", "SlicedFrame", "render_slice", "cut_slice_into",
+           "mesh_color", "MeshColorizer", "VertexColors"]

@@ -85,27 +85,34 @@ def marching_tetrahedra(volume, level=0.0, spacing=(1.0, 1.0, 1.0), normals=True
 
 class ExtractedMesh:
     """V [V,3] f32 world positions, F [F,3] i32, NV [V,3] f32 outward unit normals or None (what the reference stores as
-    `NV = -normals`, sdf_utils.py:288); `edges` [V,2] i64 and `volume` [n,n,n] when requested; `nr_evaluated` grid points."""
+    `NV = -normals`, sdf_utils.py:288); `edges` [V,2] i64 and `volume` [n,n,n] when requested; `nr_evaluated` grid points;
+    C [V,3] u8 per-vertex colours or None (mesh_color.MeshColorizer.colorize)."""
 
-    def __init__(self, V, F, NV=None, edges=None, volume=None, nr_evaluated=0):
-        self.V, self.F, self.NV, self.edges, self.volume, self.nr_evaluated = V, F, NV, edges, volume, nr_evaluated
+    def __init__(self, V, F, NV=None, edges=None, volume=None, nr_evaluated=0, C=None):
+        self.V, self.F, self.NV, self.edges, self.volume, self.nr_evaluated, self.C = V, F, NV, edges, volume, nr_evaluated, C
 
     def cpu(self):
         c = lambda t: None if t is None else t.cpu()    # noqa: E731
-        return ExtractedMesh(c(self.V), c(self.F), c(self.NV), c(self.edges), c(self.volume), self.nr_evaluated)
+        return ExtractedMesh(c(self.V), c(self.F), c(self.NV), c(self.edges), c(self.volume), self.nr_evaluated, c(self.C))
 
     def save_ply(self, path):
         """binary little-endian PLY in the layout of compat/easypbr Mesh.save_to_file: 12 (24 with normals) bytes per vertex,
-        13 per face"""
+        13 per face; with colours `C`, `uchar red, green, blue` after them: 15 (27) bytes per vertex"""
         import numpy as np
         V = self.V.detach().cpu().numpy().astype("<f4").reshape(-1, 3)
         F = self.F.detach().cpu().numpy().astype("<i4").reshape(-1, 3)
         has_n = self.NV is not None and len(self.NV) == len(V) and len(V) > 0
+        has_c = self.C is not None and len(self.C) == len(V) and len(V) > 0
         props = "property float x\nproperty float y\nproperty float z\n" + (
-            "property float nx\nproperty float ny\nproperty float nz\n" if has_n else "")
+            "property float nx\nproperty float ny\nproperty float nz\n" if has_n else "") + (
+            "property uchar red\nproperty uchar green\nproperty uchar blue\n" if has_c else "")
         header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%selement face %d\nproperty list uchar int "
                   "vertex_indices\nend_header\n" % (len(V), props, len(F)))
         vert = np.concatenate([V, self.NV.detach().cpu().numpy().astype("<f4").reshape(-1, 3)], 1) if has_n else V
+        if has_c:       # a packed record per vertex: the floats, then three bytes
+            rec = np.empty(len(V), dtype=[("f", "<f4", (vert.shape[1],)), ("c", "u1", (3,))])
+            rec["f"], rec["c"] = vert, self.C.detach().cpu().numpy().astype("u1").reshape(-1, 3)
+            vert = rec
         face = np.empty(len(F), dtype=[("n", "u1"), ("i", "<i4", (3,))])
         face["n"], face["i"] = 3, F
         os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)

@@ -219,6 +219,11 @@ def _filter(mesh, keep, face_mask, who):
         L.call("psdf_mesh_clean_emit_faces", L.ptr(F), L.c_l(nF), L.ptr(face_keep), L.ptr(fincl), L.ptr(vertex_map), L.ptr(F_out),
                L.stream())
     out = ExtractedMesh(V_out, F_out, NV_out, edges_out, getattr(mesh, "volume", None), getattr(mesh, "nr_evaluated", 0))
+    C = getattr(mesh, "C", None)
+    if C is not None and len(C) == nV:      # per-vertex colours (mesh_color.py): the kept vertices', in their order
+        # a stable sort of the flags lists the kept vertices first, in their order; their number is known: no second host read
+        kept = torch.argsort(keep, descending=True, stable=True)[:kept_v]
+        out.C = C.to(dev).index_select(0, kept)
     out.vertex_map, out.face_keep = vertex_map, face_keep.to(torch.bool)
     return out
 
@@ -227,8 +232,8 @@ def _filter(mesh, keep, face_mask, who):
 def filter_vertices(mesh_or_VF, keep):
     """-> ExtractedMesh with `.vertex_map` [nV] int32 (-1 where removed) and `.face_keep` [nF] bool:
     evaluate_chamfer_distance.py:146-155 and remove_marked_vertices(mask, True).  Kept vertices stay in their old order, a face
-    survives iff all three of its vertices do, surviving faces stay in their old order and are renumbered; `NV` and `edges` are
-    carried along.  A face naming a vertex outside [0, nV) raises ValueError.  One host read."""
+    survives iff all three of its vertices do, surviving faces stay in their old order and are renumbered; `NV`, `edges` and
+    the per-vertex colours `C` are carried along.  A face naming a vertex outside [0, nV) raises ValueError.  One host read."""
     return _filter(_mesh_of(mesh_or_VF), keep, None, "filter_vertices")
 
 

@@ -379,6 +379,20 @@ class FrameRenderer:
         self.trainer._params_ready()
         return render_slice(self.trainer.sdf, plane, self.box() if box is None else box, size, **kw)
 
+    def mesh_colorizer(self, it=None):
+        """-> mesh_color.MeshColorizer over the SDF and the colour network (`it` None: the lattice window fully open)"""
+        from .mesh_color import MeshColorizer
+        self.trainer._params_ready()
+        return MeshColorizer(self.trainer.sdf, self.trainer.rgb, it)
+
+    def colored_mesh(self, nr_points_per_dim, min_val=-0.5, max_val=0.5, it=None, **extract_kw):
+        """-> mesh.ExtractedMesh of the SDF's zero set with per-vertex colours `C` [V, 3] uint8 (each vertex seen head-on from
+        outside); extract_kw: MeshExtractor.extract's"""
+        from .mesh import MeshExtractor
+        colorizer = self.mesh_colorizer(it)
+        mesh = MeshExtractor.from_sdf_net(self.trainer.sdf, colorizer.it).extract(nr_points_per_dim, min_val, max_val, **extract_kw)
+        return colorizer.colorize(mesh)
+
     def render_views(self, frames, mode="volumetric", **kwargs):
         """-> [N, 3, H, W] float32: the rgb of every frame (all of one size), ready for image_eval.evaluate_views; mode
         "volumetric": `render`, "traced": `render_traced`"""
