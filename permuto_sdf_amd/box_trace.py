@@ -23,6 +23,7 @@ stay in their slots, masked out of the evaluations, instead of being compacted a
 points are the compacting loop's bit for bit (tests/test_gpu_box_trace.py).  CPU tensors raise PsdfError: there is no CPU path.
 """
 import dataclasses
+import functools
 from typing import Optional
 
 import numpy as np
@@ -30,6 +31,7 @@ import torch
 
 from . import _lib as L
 from .bridge import OccupancyGrid
+from .frame import FramePlan, frame_device, frame_rays, new_planes, open_window
 from .net_eval import masked_sdf, masked_sdf_gradient, one_row_head
 
 
@@ -211,18 +213,10 @@ def box_trace_resolve_raw(tracer, origins, dirs, coverage_tresh, height, width, 
 
 
 def _frame_setup(net, frame, it, camera_normals, max_rays_per_chunk):
-    from .render import _IT_WINDOW_OPEN, FramePlan
-    L.require_cuda(frame.K, frame.tf_world_cam)
-    dev = net.encoding.lattice_values.device
-    if frame.K.device != dev or frame.tf_world_cam.device != dev:
-        raise L.PsdfError("the frame lives on %s, the net on %s" % (frame.K.device, dev))
-    H, W = frame.height, frame.width
-    plan = FramePlan(H, W, 1, max_rays_per_chunk)
-    window = net.window(_IT_WINDOW_OPEN if it is None else it)
-
-    def planes(c):
-        return torch.empty((c, H, W), dtype=torch.float32, device=dev)      # every pixel belongs to one chunk, which writes it
-
+    dev = frame_device(frame, net)
+    plan = FramePlan(frame.height, frame.width, 1, max_rays_per_chunk)
+    window = open_window(net, it)
+    planes = functools.partial(new_planes, frame, dev=dev)
     out = BoxTracedFrame(normals=planes(3), normals_cam=planes(3) if camera_normals else None, weights_sum=planes(1), depth=planes(1))
     return plan, window, out, (frame.rot_cam_world() if camera_normals else None)
 
@@ -235,9 +229,8 @@ def render_box_traced(net, box, frame, it=None, time_val=None, nr_sphere_traces=
                       coverage_tresh=0.01, camera_normals=False, max_rays_per_chunk=_POOL):
     """-> BoxTracedFrame of the field of `net` (anything with `encoding`, `mlp_sdf` and `window(it)`) inside `box`, at
     `time_val` for a 4-D net.  it: the iteration whose coarse-to-fine window is used (None: fully open).  coverage_tresh:
-    filter_unconverged_points' (sdf_utils.py:221).  Chunks of at most max_rays_per_chunk rays (render.FramePlan with one
+    filter_unconverged_points' (sdf_utils.py:221).  Chunks of at most max_rays_per_chunk rays (frame.FramePlan with one
     sample per ray); per chunk: rays -> trace -> one resolve launch.  No host wait."""
-    from .render import frame_rays
     plan, window, out, rot = _frame_setup(net, frame, it, camera_normals, max_rays_per_chunk)
     tracer = BoxTracer(net.encoding, net.mlp_sdf, box, window)
     for first, count in plan.chunks():
@@ -254,7 +247,6 @@ class BoxPlayer:
 
     def __init__(self, net, box, frame, it=None, coverage_tresh=0.01, camera_normals=False, max_rays_per_chunk=_POOL,
                  nr_sphere_traces=20, sdf_multiplier=0.9, sdf_converged_tresh=2e-4):
-        from .render import frame_rays
         plan, window, self._frame_out, rot = _frame_setup(net, frame, it, camera_normals, max_rays_per_chunk)
         if plan.nr_chunks != 1:
             raise ValueError("BoxPlayer plays a frame of one chunk: %d x %d is %d chunks of %d rays (render_box_traced takes any "

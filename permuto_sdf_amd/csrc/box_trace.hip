@@ -16,19 +16,12 @@
 //
 // One thread per ray, one-dimensional grid, no cross-lane operation, no LDS: the file also compiles as C++ against
 // tests/host/hip_on_host, where tests/host/box_trace_kernels_check.cpp runs it.  The entries allocate nothing and never synchronise.
-#include "composite_device.h"
-#include "frame_plan.h"
+#include "frame_device.h"
 #include "../../include/psdf.h"
 
 using namespace psdf;
 
 namespace {
-
-struct Triple {
-  float v[3];
-};
-
-__host__ inline Triple triple(const float* p) { return Triple{{p[0], p[1], p[2]}}; }
 
 struct BoxHit {
   float t_entry, t_exit;
@@ -52,15 +45,6 @@ __device__ __forceinline__ BoxHit box_intersect(const Triple& bmin, const Triple
   if (invalid) lo = hi = 0.f;
   lo = lo < 0.f ? 0.f : lo;
   return BoxHit{lo, hi, !invalid};
-}
-
-// aabb.py:28-42: strictly inside on all three axes
-__device__ __forceinline__ bool box_inside(const Triple& tr, const Triple& half, v3 p) {
-  const float q[3] = {p.x - tr.v[0], p.y - tr.v[1], p.z - tr.v[2]};
-  bool in = true;
-#pragma unroll
-  for (int i = 0; i < 3; i++) in = in && q[i] < half.v[i] && q[i] > -half.v[i];
-  return in;
 }
 
 __global__ void __launch_bounds__(PSDF_BLOCK)
@@ -111,12 +95,6 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   if (done) converged[i] = 1;
 }
 
-__device__ __forceinline__ void st_planes(float* __restrict__ img, int64_t plane, int64_t pixel, v3 a) {
-  img[pixel] = a.x;
-  img[plane + pixel] = a.y;
-  img[2 * plane + pixel] = a.z;
-}
-
 __global__ void __launch_bounds__(PSDF_BLOCK)
     box_trace_resolve_kernel(int nr_rays, int stride, const float* __restrict__ origins, const float* __restrict__ dirs,
                              const float* __restrict__ pts, const float* __restrict__ sdf_end, const float* __restrict__ gradients,
@@ -126,25 +104,13 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   const int i = blockIdx.x * PSDF_BLOCK + threadIdx.x;
   if (i >= nr_rays) return;
   const int64_t pixel = pixel_first + i;
-  v3 nrm = mk3(0.f, 0.f, 0.f), cam = nrm;
-  float weight = 0.f, depth = 0.f;
+  SurfacePixel px;
   // filter_unconverged_points, sdf_utils.py:226: a signed compare (a NaN is not covered)
   if (!no_hit[i] && sdf_end[i] < coverage_thresh) {
     const v3 o = ld3(origins + 3 * (int64_t)i), d = ld3(dirs + 3 * (int64_t)i);
-    const v3 q = ld3(pts + (int64_t)stride * i) - o;
-    nrm = normalize_eps(ld3(gradients + (int64_t)stride * i)).y;
-    if (normals_cam_img) {
-      const v3 c = mk3(rot[0] * nrm.x + rot[1] * nrm.y + rot[2] * nrm.z, rot[3] * nrm.x + rot[4] * nrm.y + rot[5] * nrm.z,
-                       rot[6] * nrm.x + rot[7] * nrm.y + rot[8] * nrm.z);
-      cam = normalize_eps(c).y;
-    }
-    weight = 1.f;
-    depth = (q.x * d.x + q.y * d.y) + q.z * d.z;
+    px = surface_hit(o, d, ld3(pts + (int64_t)stride * i), ld3(gradients + (int64_t)stride * i), normals_cam_img ? rot : nullptr);
   }
-  st_planes(normals_img, plane, pixel, nrm);
-  if (normals_cam_img) st_planes(normals_cam_img, plane, pixel, cam);
-  weights_sum_img[pixel] = weight;
-  depth_img[pixel] = depth;
+  st_surface(px, plane, pixel, normals_img, normals_cam_img, weights_sum_img, depth_img);
 }
 
 }  // namespace
@@ -194,12 +160,9 @@ int psdf_box_trace_resolve(int nr_rays, int stride, const float* origins, const 
   if (!origins || !dirs || !pts || !sdf_end || !gradients || !no_hit || !normals_img || !weights_sum_img || !depth_img)
     return PSDF_ERR_ARG;
   if (normals_cam_img && !rot_cam_world) return PSDF_ERR_ARG;
-  if (H < 1 || W < 1) return PSDF_ERR_ARG;
-  const int64_t pixels = (int64_t)H * W;
-  if (pixels > psdf::frame_plan::MAX_PIXELS) return PSDF_ERR_UNSUPPORTED;
-  if (pixel_first < 0 || pixel_first > pixels - nr_rays) return PSDF_ERR_ARG;
+  if (const int range = frame_plan::check_range(H, W, pixel_first, nr_rays)) return range;
   hipLaunchKernelGGL(box_trace_resolve_kernel, dim3(psdf_blocks(nr_rays, PSDF_BLOCK)), dim3(PSDF_BLOCK), 0, (hipStream_t)stream,
-                     nr_rays, stride, origins, dirs, pts, sdf_end, gradients, no_hit, coverage_thresh, rot_cam_world, pixels,
+                     nr_rays, stride, origins, dirs, pts, sdf_end, gradients, no_hit, coverage_thresh, rot_cam_world, (int64_t)H * W,
                      pixel_first, normals_img, normals_cam_img, weights_sum_img, depth_img);
   PSDF_LAUNCH_CHECK();
   return PSDF_OK;

@@ -28,19 +28,13 @@
 // plane (z 4), nothing written per sample; per ray 8 B of range read, 4 B of transmittance and 16 B of planes written (20 B
 // with the depth plane).
 // Any ray length; no LDS; nothing allocates and nothing synchronises.
-#include "composite_device.h"
+#include "frame_device.h"
 #include "frame_plan.h"
 #include "../../include/psdf.h"
 
 using namespace psdf;
 
 namespace {
-
-__device__ __forceinline__ void st_planes(float* __restrict__ img, int64_t plane, int64_t pixel, v3 a) {
-  img[pixel] = a.x;
-  img[plane + pixel] = a.y;
-  img[2 * plane + pixel] = a.z;
-}
 
 __global__ void __launch_bounds__(PSDF_BLOCK)
     frame_composite_neus_kernel(int nr_rays, RayIndex ri, const float* __restrict__ sdf, const float* __restrict__ dirs,
@@ -95,11 +89,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
       st_planes(rgb_img, plane, pixel, mk3(r, g, b));
       const v3 nrm = normalize_eps(mk3(gx, gy, gz)).y;
       st_planes(normals_img, plane, pixel, nrm);
-      if (normals_cam_img) {
-        const v3 c = mk3(rot[0] * nrm.x + rot[1] * nrm.y + rot[2] * nrm.z, rot[3] * nrm.x + rot[4] * nrm.y + rot[5] * nrm.z,
-                         rot[6] * nrm.x + rot[7] * nrm.y + rot[8] * nrm.z);
-        st_planes(normals_cam_img, plane, pixel, normalize_eps(c).y);
-      }
+      if (normals_cam_img) st_planes(normals_cam_img, plane, pixel, camera_normal(rot, nrm));
       weights_sum_img[pixel] = ws;
       transmittance[ray] = T_bg;
     }
@@ -175,14 +165,7 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   }
 }
 
-// the pixel range [pixel_first, pixel_first + nr_rays) of an H x W frame: 0, or the code to return
-inline int check_range(int nr_rays, int H, int W, int64_t pixel_first) {
-  if (H < 1 || W < 1) return PSDF_ERR_ARG;
-  const int64_t pixels = (int64_t)H * W;
-  if (pixels > psdf::frame_plan::MAX_PIXELS) return PSDF_ERR_UNSUPPORTED;
-  if (pixel_first < 0 || pixel_first > pixels - nr_rays) return PSDF_ERR_ARG;
-  return PSDF_OK;
-}
+// the pixel range [pixel_first, pixel_first + nr_rays) of an H x W frame: frame_plan::check_range, 0 or the code to return
 
 }  // namespace
 
@@ -198,8 +181,7 @@ int psdf_frame_composite_neus(int nr_rays, const int* start_end, int equal, int 
   if (max_nr_samples < 0 || (equal && fixed < 0) || (normals_cam_img && !rot_cam_world)) return PSDF_ERR_ARG;
   // a container without samples may come without sample tensors: every ray takes the empty branch
   if (max_nr_samples > 0 && (!sdf || !dirs || !gradients || !dt || !rgb)) return PSDF_ERR_ARG;
-  const int status = check_range(nr_rays, H, W, pixel_first);
-  if (status != PSDF_OK) return status;
+  if (const int status = frame_plan::check_range(H, W, pixel_first, nr_rays)) return status;
   hipLaunchKernelGGL(frame_composite_neus_kernel, dim3(ray_grid(nr_rays)), dim3(PSDF_BLOCK), 0, (hipStream_t)stream, nr_rays,
                      RayIndex{start_end, equal, fixed, max_nr_samples}, sdf, dirs, gradients, dt, rgb, inv_s, cos_anneal_ratio,
                      rot_cam_world, (int64_t)H * W, pixel_first, rgb_img, normals_img, normals_cam_img, weights_sum_img,
@@ -215,8 +197,7 @@ int psdf_frame_composite_nerf(int nr_rays, const int* start_end, int equal, int 
   if (!transmittance || !rgb_img || !rgb_bg_img || (!equal && !start_end)) return PSDF_ERR_ARG;
   if (max_nr_samples < 0 || (equal && fixed < 0)) return PSDF_ERR_ARG;
   if (max_nr_samples > 0 && (!raw_density || !dt || !rgb)) return PSDF_ERR_ARG;
-  const int status = check_range(nr_rays, H, W, pixel_first);
-  if (status != PSDF_OK) return status;
+  if (const int status = frame_plan::check_range(H, W, pixel_first, nr_rays)) return status;
   hipLaunchKernelGGL(frame_composite_nerf_kernel, dim3(ray_grid(nr_rays)), dim3(PSDF_BLOCK), 0, (hipStream_t)stream, nr_rays,
                      RayIndex{start_end, equal, fixed, max_nr_samples}, raw_density, dt, rgb, transmittance, (int64_t)H * W,
                      pixel_first, rgb_img, rgb_bg_img);
@@ -232,8 +213,7 @@ int psdf_nerf_frame_render(int nr_rays, const int* start_end, int equal, int fix
   if (max_nr_samples < 0 || (equal && fixed < 0)) return PSDF_ERR_ARG;
   // a container without samples may come without sample tensors; z is read for the depth plane alone
   if (max_nr_samples > 0 && (!raw_density || !dt || !rgb || (depth_img && !z))) return PSDF_ERR_ARG;
-  const int status = check_range(nr_rays, H, W, pixel_first);
-  if (status != PSDF_OK) return status;
+  if (const int status = frame_plan::check_range(H, W, pixel_first, nr_rays)) return status;
   hipLaunchKernelGGL(frame_render_nerf_kernel, dim3(ray_grid(nr_rays)), dim3(PSDF_BLOCK), 0, (hipStream_t)stream, nr_rays,
                      RayIndex{start_end, equal, fixed, max_nr_samples}, raw_density, dt, z, rgb, (int64_t)H * W, pixel_first,
                      rgb_img, weights_sum_img, depth_img, transmittance);

@@ -1,5 +1,6 @@
-// frame_plan.h -- the host arithmetic behind the chunking of a rendered frame (render.py, frame_rays.hip, frame_composite.hip):
-// how many rays one chunk holds, how many chunks a frame takes and how long the last one is.  Integers only: no HIP, no device,
+// frame_plan.h -- the host arithmetic behind the chunking of a rendered frame (frame.py, frame_rays.hip, frame_composite.hip):
+// how many rays one chunk holds, how many chunks a frame takes and how long the last one is, and the ONE check of a chunk of
+// pixels (or of the cells of a layer) that every writer of image planes makes.  Integers only: no HIP, no device,
 // no state -- a plain C++17 compiler accepts this header, and tests/host/frame_plan_check.cpp runs it under the address and
 // undefined-behaviour sanitizers.
 //
@@ -18,7 +19,7 @@ namespace frame_plan {
 constexpr int PLAN_OK = 0, PLAN_ERR_ARG = -1, PLAN_ERR_UNSUPPORTED = -2;
 
 constexpr int RAY_MULTIPLE = 64;
-constexpr int64_t MAX_PIXELS = 0x7fffffffll;   // pixel indices are int32: H W < 2^31
+constexpr int64_t MAX_PIXELS = 0x7fffffffll;   // pixel and cell indices are int32: H W < 2^31, S S < 2^31
 
 struct Plan {
   int status;                // PLAN_OK, or why there is no plan (every other field 0)
@@ -45,6 +46,15 @@ inline Plan plan(int H, int W, int max_nr_samples_per_ray, int64_t pool_samples)
   p.chunks = (pixels + rays - 1) / rays;
   p.last_chunk = pixels - (p.chunks - 1) * rays;
   return p;
+}
+
+// the elements [first, first + count) of a rows x cols image (the pixels of a frame, the cells of a layer): PLAN_OK or the refusal
+inline int check_range(int rows, int cols, int64_t first, int64_t count) {
+  if (rows < 1 || cols < 1 || count < 1) return PLAN_ERR_ARG;
+  const int64_t elements = (int64_t)rows * cols;
+  if (elements > MAX_PIXELS) return PLAN_ERR_UNSUPPORTED;
+  if (first < 0 || first > elements - count) return PLAN_ERR_ARG;
+  return PLAN_OK;
 }
 
 }  // namespace frame_plan

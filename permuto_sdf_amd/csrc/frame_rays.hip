@@ -14,6 +14,7 @@
 
 using namespace psdf;
 namespace fplan = psdf::frame_plan;
+static_assert(fplan::PLAN_OK == PSDF_OK && fplan::PLAN_ERR_ARG == PSDF_ERR_ARG && fplan::PLAN_ERR_UNSUPPORTED == PSDF_ERR_UNSUPPORTED);
 
 namespace {
 
@@ -54,10 +55,8 @@ int psdf_frame_plan(int H, int W, int max_nr_samples_per_ray, int64_t pool_sampl
 int psdf_frame_rays(int H, int W, const float* K, const float* tf_world_cam, int64_t pixel_first, int nr_rays, float* origins,
                     float* dirs, void* stream) {
   if (nr_rays <= 0) return PSDF_OK;
-  if (H < 1 || W < 1 || !K || !tf_world_cam || !origins || !dirs) return PSDF_ERR_ARG;
-  const int64_t pixels = (int64_t)H * W;
-  if (pixels > fplan::MAX_PIXELS) return PSDF_ERR_UNSUPPORTED;
-  if (pixel_first < 0 || pixel_first > pixels - nr_rays) return PSDF_ERR_ARG;
+  if (!K || !tf_world_cam || !origins || !dirs) return PSDF_ERR_ARG;
+  if (const int range = fplan::check_range(H, W, pixel_first, nr_rays)) return range;
   hipLaunchKernelGGL(frame_rays_kernel, dim3(psdf_blocks(nr_rays, PSDF_BLOCK)), dim3(PSDF_BLOCK), 0, (hipStream_t)stream, nr_rays,
                      (int)pixel_first, W, K, tf_world_cam, origins, dirs);
   PSDF_LAUNCH_CHECK();

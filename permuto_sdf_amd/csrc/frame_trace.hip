@@ -12,25 +12,19 @@
 //   normals_cam  normalize_eps(R n), R the rotation of tf_cam_world (optional)   0
 //   weights_sum  1                                                               0
 //   depth        ((px - ox) dx + (py - oy) dy) + (pz - oz) dz, p = pos[slot]     0
-// at pixel pixel_first + ray.  Every pixel of the chunk is written exactly once: the planes need no zero fill.
+// at pixel pixel_first + ray: the surface pixel of frame_device.h (surface_hit, st_surface) and the colour beside it.
+// Every pixel of the chunk is written exactly once: the planes need no zero fill.
 // HBM traffic per ray: 28 B read (slot 4, origin 12, direction 12) and, for a valid ray, 36 B more (pos, gradient, rgb); 32 B
 // written (44 B with camera normals).
 //
 // One thread per ray, one-dimensional grid, no cross-lane operation, no LDS: the file also compiles as C++ against
 // tests/host/hip_on_host, where tests/host/frame_trace_check.cpp runs it.  The entry allocates nothing and never synchronises.
-#include "composite_device.h"
-#include "frame_plan.h"
+#include "frame_device.h"
 #include "../../include/psdf.h"
 
 using namespace psdf;
 
 namespace {
-
-__device__ __forceinline__ void st_planes(float* __restrict__ img, int64_t plane, int64_t pixel, v3 a) {
-  img[pixel] = a.x;
-  img[plane + pixel] = a.y;
-  img[2 * plane + pixel] = a.z;
-}
 
 __global__ void __launch_bounds__(PSDF_BLOCK)
     trace_frame_resolve_kernel(int nr_rays, const int* __restrict__ slot, const float* __restrict__ origins,
@@ -42,26 +36,15 @@ __global__ void __launch_bounds__(PSDF_BLOCK)
   if (i >= nr_rays) return;
   const int64_t pixel = pixel_first + i;
   const int s = slot[i];
-  v3 colour = mk3(0.f, 0.f, 0.f), nrm = colour, cam = colour;
-  float weight = 0.f, depth = 0.f;
+  v3 colour = mk3(0.f, 0.f, 0.f);
+  SurfacePixel px;
   if (s >= 0) {
     const v3 o = ld3(origins + 3 * (int64_t)i), d = ld3(dirs + 3 * (int64_t)i);
-    const v3 q = ld3(pos + 3 * (int64_t)s) - o;
     colour = ld3(rgb + 3 * (int64_t)s);
-    nrm = normalize_eps(ld3(gradients + 3 * (int64_t)s)).y;
-    if (normals_cam_img) {
-      const v3 c = mk3(rot[0] * nrm.x + rot[1] * nrm.y + rot[2] * nrm.z, rot[3] * nrm.x + rot[4] * nrm.y + rot[5] * nrm.z,
-                       rot[6] * nrm.x + rot[7] * nrm.y + rot[8] * nrm.z);
-      cam = normalize_eps(c).y;
-    }
-    weight = 1.f;
-    depth = (q.x * d.x + q.y * d.y) + q.z * d.z;
+    px = surface_hit(o, d, ld3(pos + 3 * (int64_t)s), ld3(gradients + 3 * (int64_t)s), normals_cam_img ? rot : nullptr);
   }
   st_planes(rgb_img, plane, pixel, colour);
-  st_planes(normals_img, plane, pixel, nrm);
-  if (normals_cam_img) st_planes(normals_cam_img, plane, pixel, cam);
-  weights_sum_img[pixel] = weight;
-  depth_img[pixel] = depth;
+  st_surface(px, plane, pixel, normals_img, normals_cam_img, weights_sum_img, depth_img);
 }
 
 }  // namespace
@@ -78,12 +61,9 @@ int psdf_trace_frame_resolve(int nr_rays, int nr_valid, const int* slot, const f
   if (normals_cam_img && !rot_cam_world) return PSDF_ERR_ARG;
   // a chunk without a valid ray may come without the dense arrays: every slot is -1
   if (nr_valid > 0 && (!pos || !gradients || !rgb)) return PSDF_ERR_ARG;
-  if (H < 1 || W < 1) return PSDF_ERR_ARG;
-  const int64_t pixels = (int64_t)H * W;
-  if (pixels > psdf::frame_plan::MAX_PIXELS) return PSDF_ERR_UNSUPPORTED;
-  if (pixel_first < 0 || pixel_first > pixels - nr_rays) return PSDF_ERR_ARG;
+  if (const int range = frame_plan::check_range(H, W, pixel_first, nr_rays)) return range;
   hipLaunchKernelGGL(trace_frame_resolve_kernel, dim3(psdf_blocks(nr_rays, PSDF_BLOCK)), dim3(PSDF_BLOCK), 0, (hipStream_t)stream,
-                     nr_rays, slot, origins, dirs, pos, gradients, rgb, rot_cam_world, pixels, pixel_first, rgb_img, normals_img,
+                     nr_rays, slot, origins, dirs, pos, gradients, rgb, rot_cam_world, (int64_t)H * W, pixel_first, rgb_img, normals_img,
                      normals_cam_img, weights_sum_img, depth_img);
   PSDF_LAUNCH_CHECK();
   return PSDF_OK;

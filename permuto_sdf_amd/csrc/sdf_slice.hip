@@ -24,11 +24,11 @@
 // t > 0, both coordinates lie in [-extent, extent), the point is strictly inside the box, and the pixel has no surface
 // (weights_sum == 0) or t < depth.
 //
-// The box test is AABB.check_point_inside_primitive (permuto_sdf_py/utils/aabb.py:28-42), strict about the translation, as
-// box_trace.hip restates it.  One thread per cell or per ray, one-dimensional grid, no cross-lane operation, no LDS, every
+// The box test is AABB.check_point_inside_primitive (permuto_sdf_py/utils/aabb.py:28-42), strict about the translation:
+// box_inside of frame_device.h, the one the box tracer steps with.  One thread per cell or per ray, one-dimensional grid, no cross-lane operation, no LDS, every
 // element written by one thread: the file also compiles as C++ against tests/host/hip_on_host, where
 // tests/host/sdf_slice_kernels_check.cpp runs it.  The entries allocate nothing and never synchronise.
-#include "psdf_common.h"
+#include "frame_device.h"
 #include "sdf_slice_plan.h"
 #include "../../include/psdf.h"
 
@@ -37,27 +37,14 @@ namespace splan = psdf::sdf_slice_plan;
 
 namespace {
 
-struct Triple {
-  float v[3];
-};
 struct Axes {
   float m[9];      // row major; column j is axis j
 };
 
-__host__ inline Triple triple(const float* p) { return Triple{{p[0], p[1], p[2]}}; }
 __host__ inline Axes axes9(const float* p) {
   Axes a;
   for (int i = 0; i < 9; i++) a.m[i] = p[i];
   return a;
-}
-
-// aabb.py:28-42: strictly inside on all three axes
-__device__ __forceinline__ bool box_inside(const Triple& tr, const Triple& half, v3 p) {
-  const float q[3] = {p.x - tr.v[0], p.y - tr.v[1], p.z - tr.v[2]};
-  bool in = true;
-#pragma unroll
-  for (int i = 0; i < 3; i++) in = in && q[i] < half.v[i] && q[i] > -half.v[i];
-  return in;
 }
 
 // common_utils.py:150-154 (x is not a NaN here)
@@ -84,12 +71,6 @@ __device__ __forceinline__ v3 iso_colour(float s, const float* __restrict__ tabl
   for (int i = 0; i < bands.n; i++)
     if (s > bands.lo[i] && s < bands.hi[i]) c = mk3(bands.rgb[i][0], bands.rgb[i][1], bands.rgb[i][2]);
   return c;
-}
-
-__device__ __forceinline__ void st_planes(float* __restrict__ img, int64_t plane, int64_t cell, v3 a) {
-  img[cell] = a.x;
-  img[plane + cell] = a.y;
-  img[2 * plane + cell] = a.z;
 }
 
 __global__ void __launch_bounds__(splan::BLOCK)
@@ -198,8 +179,7 @@ int psdf_slice_points(int S, int64_t first, int count, int stride, const float* 
                       const float* translation, const float* half, const float* time, float* pts, uint8_t* skip, void* stream) {
   if (count == 0) return PSDF_OK;
   if (splan::check_stride(stride) != splan::PLAN_OK) return PSDF_ERR_ARG;
-  const int range = splan::check_range(S, S, first, count);
-  if (range != splan::PLAN_OK) return range;
+  if (const int range = frame_plan::check_range(S, S, first, count)) return range;
   if (!axes || !translation || !half || !pts || !skip || (stride == 4 && !time)) return PSDF_ERR_ARG;
   hipLaunchKernelGGL(slice_points_kernel, dim3(splan::grid(count)), dim3(splan::BLOCK), 0, (hipStream_t)stream, count, (int)first, S,
                      stride, axes9(axes), z, extent_scale, triple(translation), triple(half), time, pts, skip);
@@ -215,8 +195,7 @@ int psdf_slice_colorize(int S, int64_t first, int count, const float* sdf, const
   splan::Bands bands;
   const int colours = colour_args(table, K, base_map, nr_lines, band_lo, band_hi, band_rgb, &base, &bands);
   if (colours != PSDF_OK) return colours;
-  const int range = splan::check_range(S, S, first, count);
-  if (range != splan::PLAN_OK) return range;
+  if (const int range = frame_plan::check_range(S, S, first, count)) return range;
   if (!sdf || !skip || !rgb || !sdf_img || !inside_img) return PSDF_ERR_ARG;
   hipLaunchKernelGGL(slice_colorize_kernel, dim3(splan::grid(count)), dim3(splan::BLOCK), 0, (hipStream_t)stream, count, first,
                      (int64_t)S * S, sdf, skip, table, K, base, bands, rgb, sdf_img, inside_img);
@@ -230,8 +209,7 @@ int psdf_slice_cut_begin(int nr_rays, int stride, const float* axes, float z, fl
                          float* t, void* stream) {
   if (nr_rays == 0) return PSDF_OK;
   if (splan::check_stride(stride) != splan::PLAN_OK) return PSDF_ERR_ARG;
-  const int range = splan::check_range(H, W, pixel_first, nr_rays);
-  if (range != splan::PLAN_OK) return range;
+  if (const int range = frame_plan::check_range(H, W, pixel_first, nr_rays)) return range;
   if (!axes || !translation || !half || !origins || !dirs || !weights_sum_img || !depth_img || !pts || !skip || !t)
     return PSDF_ERR_ARG;
   if (stride == 4 && !time) return PSDF_ERR_ARG;
@@ -251,8 +229,7 @@ int psdf_slice_cut_resolve(int nr_rays, const float* sdf, const uint8_t* skip, c
   splan::Bands bands;
   const int colours = colour_args(table, K, base_map, nr_lines, band_lo, band_hi, band_rgb, &base, &bands);
   if (colours != PSDF_OK) return colours;
-  const int range = splan::check_range(H, W, pixel_first, nr_rays);
-  if (range != splan::PLAN_OK) return range;
+  if (const int range = frame_plan::check_range(H, W, pixel_first, nr_rays)) return range;
   if (!sdf || !skip || !t || !rgb_img || !depth_img || !weights_sum_img || !slice_mask_img) return PSDF_ERR_ARG;
   hipLaunchKernelGGL(slice_cut_resolve_kernel, dim3(splan::grid(nr_rays)), dim3(splan::BLOCK), 0, (hipStream_t)stream, nr_rays,
                      pixel_first, (int64_t)H * W, sdf, skip, t, table, K, base, bands, rgb_img, depth_img, weights_sum_img,

@@ -12,7 +12,7 @@ That is `ManualTrainer._fg_forward`'s chain over the raw feature-major kernels, 
 colour encoding was written into (no SH launch, no normalize launch, no torch.cat, no transpose), `psdf_mesh_color_finish`
 turns the head's output into float and 8-bit colours in place in the result.  A vertex has no ray, so its view direction is made
 up: `view="normal"` looks at every vertex head-on from outside (d = -normal: a view-independent "albedo-like" colour),
-a `render.Frame` or a 3-vector looks from that camera centre (d = normalize(p - eye), no visibility test).
+a `frame.Frame` or a 3-vector looks from that camera centre (d = normalize(p - eye), no visibility test).
 
 Evaluation mode as `FrameRenderer.render`: the lattice window fully open unless `it` is given, no colour calibration
 (create_my_images.py passes None).  Vertices are streamed in the chunks of `ColorPlan`; the buffers this module owns are allocated
@@ -29,11 +29,11 @@ from typing import NamedTuple
 import torch
 
 from . import _lib as L
+from .frame import IT_WINDOW_OPEN as _IT_WINDOW_OPEN
 from .mlp import lipshitz_normalize_all_raw, mlp_forward_raw, mlp_forward_wide_f16_raw, pack_params
 from .net_eval import enc_forward, net_params, sdf_gradient
 
 _PLAN_FIELDS = 7            # PSDF_MESH_COLOR_PLAN_FIELDS of include/psdf.h
-_IT_WINDOW_OPEN = 9999999   # as render.py: far past the coarse-to-fine schedule, every lattice level fully open
 MODE_NORMAL, MODE_CAMERA = 0, 1     # csrc/mesh_color_plan.h
 
 

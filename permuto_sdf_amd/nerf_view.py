@@ -14,7 +14,7 @@ pred_weights_sum_img.  Here
   * `NerfFrameRenderer.from_checkpoint(folder, device)` the same from the file set of `NerfTrainer.save_checkpoint`;
   * `NerfFrameRenderer.render_views(frames)`  -> [N, 3, H, W], what `image_eval.evaluate_views` takes.
 
-The camera, its rays and the chunking are render.py's (`Frame`, `frame_rays`, `FramePlan`: the largest multiple of 64 rays whose
+The camera, its rays and the chunking are frame.py's (`Frame`, `frame_rays`, `FramePlan`: the largest multiple of 64 rays whose
 samples cannot overflow the march's pool).  Per chunk: rays -> the trainer's sampling without jitter (sphere intersection,
 occupancy march, compaction: one host wait, as in a training step) -> the foreground net over the raw feature-major kernels
 (`NerfTrainer._branch_forward`; skipped for a chunk without foreground samples) -> one launch that writes radiance, weight sum,
@@ -28,6 +28,7 @@ renders views with model_colorcal=None, train_nerf.py:107): of a run trained wit
 the calibration of the fixed image, the identity.  No image files.  CPU tensors raise PsdfError: there is no CPU path.
 """
 import dataclasses
+import functools
 import os
 from types import SimpleNamespace
 from typing import Optional
@@ -36,10 +37,9 @@ import torch
 
 from . import _lib as L
 from .bridge import OccupancyGrid, Sphere
+from .frame import IT_WINDOW_OPEN, FramePlan, frame_device, frame_rays, new_planes, sample_pool, stack_views
 from .nerf_train import FILES, HyperParams, NerfNet, NerfTrainer
-from .render import FramePlan, frame_composite_nerf_raw, frame_rays
-
-IT_WINDOW_OPEN = 9999999    # far past both coarse-to-fine schedules: every lattice level fully open
+from .render import frame_composite_nerf_raw
 
 
 def frame_render_nerf_raw(rs, raw_density, rgb, height, width, pixel_first, rgb_img, weights_sum_img, transmittance, depth_img=None):
@@ -86,15 +86,6 @@ class NerfFrameRenderer:
         return NerfFrameRenderer(SimpleNamespace(net=net, net_bg=net_bg, grid=grid, sphere=Sphere(0.5, [0, 0, 0]), hp=hp,
                                                  with_mask=bool(with_mask), iter=IT_WINDOW_OPEN))
 
-    def _check_devices(self, frame):
-        """the kernels take raw pointers: no one else would notice a frame on another device than the models"""
-        L.require_cuda(frame.K, frame.tf_world_cam)
-        dev = frame.K.device
-        models_dev = self.trainer.net.encoding.lattice_values.device
-        if dev != models_dev or frame.tf_world_cam.device != dev:
-            raise L.PsdfError("the frame lives on %s, the models on %s" % (dev, models_dev))
-        return dev
-
     def _chunk(self, frame, first, count, it, out, transmittance):
         """one chunk, start to finish; nothing it allocates outlives it"""
         t = self.trainer
@@ -118,32 +109,19 @@ class NerfFrameRenderer:
         depth: also the expected depth sum w z of the foreground."""
         t = self.trainer
         hp = t.hp
-        dev = self._check_devices(frame)
-        H, W = frame.height, frame.width
-        plan = FramePlan(H, W, hp.max_nr_samples_per_ray, pool_samples)
+        dev = frame_device(frame, t.net)
+        plan = FramePlan(frame.height, frame.width, hp.max_nr_samples_per_ray, pool_samples)
         if it is None:
             it = getattr(t, "iter", IT_WINDOW_OPEN)
-
-        def planes(c):
-            return torch.empty((c, H, W), dtype=torch.float32, device=dev)      # every pixel belongs to one chunk, which writes it
-
+        planes = functools.partial(new_planes, frame, dev=dev)
         out = NerfRenderedFrame(rgb=planes(3), rgb_bg=None if t.with_mask else planes(3), weights_sum=planes(1),
                                 depth=planes(1) if depth else None)
         transmittance = torch.empty(plan.rays_per_chunk, dtype=torch.float32, device=dev)
-        grid_pool = t.grid.max_nr_samples
-        t.grid.max_nr_samples = int(pool_samples)        # the pool the plan was made for
-        try:
+        with sample_pool(t.grid, pool_samples):
             for first, count in plan.chunks():
                 self._chunk(frame, first, count, it, out, transmittance)
-        finally:
-            t.grid.max_nr_samples = grid_pool
         return out
 
     def render_views(self, frames, **kwargs):
         """-> [N, 3, H, W] float32: the rgb of every frame (all of one size), ready for image_eval.evaluate_views"""
-        frames = list(frames)
-        if not frames:
-            raise ValueError("render_views needs at least one frame")
-        if len({(f.height, f.width) for f in frames}) != 1:
-            raise ValueError("render_views takes frames of one size")
-        return torch.stack([self.render(f, **kwargs).rgb for f in frames])
+        return stack_views(self.render, frames, **kwargs)

@@ -1,12 +1,11 @@
 """Frame renderer: a held-out view rendered on the device into planar images, volumetrically (csrc/frame_rays.hip,
-csrc/frame_composite.hip, csrc/frame_plan.h) or sphere-traced (csrc/sampling.hip: trace_select_*, csrc/frame_trace.hip).
+csrc/frame_composite.hip, csrc/frame_plan.h) or sphere-traced (csrc/sampling.hip: trace_select_*, csrc/frame_trace.hip).  The
+camera, its rays and the chunking are frame.py's; `Frame`, `FramePlan` and `frame_rays` are importable from here as well.
 
 The reference renders its evaluation views with permuto_sdf_py/experiments/evaluation/create_my_images.py: run_net_in_chunks
 (train_permuto_sdf.py:172-209) over create_rays_from_frame (nerf_utils.py:459-500), 3 000 rays per chunk, every chunk's
 results appended to Python lists, concatenated, and transposed into images (lin2nchw).  Here
 
-  * `Frame(K, tf_world_cam, height, width)`   a pinhole camera; `Frame.from_reel(reel, i)` takes image i of an image reel;
-  * `frame_rays(frame, first, count)`         the rays of a range of pixels, bit-for-bit the rays training draws for them;
   * `FrameRenderer(trainer).render(frame)`    -> `RenderedFrame`: rgb, rgb_bg, normals, normals_cam, weights_sum as [C, H, W]
                                               float32 tensors on the device;
   * `FrameRenderer(trainer).render_traced(frame)` -> `TracedFrame`: rgb, normals, normals_cam, weights_sum, depth of the
@@ -43,79 +42,14 @@ from typing import Optional
 import torch
 
 from . import _lib as L
+from .box_trace import Box
 from .bridge import OccupancyGrid, Sphere
 from .encoding import PermutoEncodingFunc
+from .frame import (IT_WINDOW_OPEN, Frame, FramePlan, _f32, frame_device, frame_rays, new_planes, sample_pool,  # noqa: F401
+                    stack_views)                      # (Frame: for the callers that know it as render.Frame)
+from .mesh_color import MeshColorizer
+from .sdf_slice import render_slice
 from .sphere_trace import SphereTracer
-
-_PLAN_FIELDS = 3            # PSDF_FRAME_PLAN_FIELDS of include/psdf.h
-_IT_WINDOW_OPEN = 9999999   # create_my_images.py:81: far past the coarse-to-fine schedule, every lattice level fully open
-
-
-class FramePlan:
-    """the chunking of an H x W frame, from the library's host-only entry (csrc/frame_plan.h decides it)"""
-
-    def __init__(self, height, width, max_nr_samples_per_ray, pool_samples):
-        out = (L.c_l * _PLAN_FIELDS)()
-        status = L.lib().psdf_frame_plan(L.c_i(int(height)), L.c_i(int(width)), L.c_i(int(max_nr_samples_per_ray)),
-                                         L.c_l(int(pool_samples)), out)
-        if status == -1:
-            raise ValueError("no chunking for a %d x %d frame with %d samples per ray out of a pool of %d (extents and the cap "
-                             "must be positive and the pool must hold 64 rays)" % (height, width, max_nr_samples_per_ray, pool_samples))
-        L.check(status, "psdf_frame_plan")
-        self.rays_per_chunk, self.nr_chunks, self.last_chunk = (int(v) for v in out)
-
-    def chunks(self):
-        """-> [(first pixel, rays)]"""
-        return [(i * self.rays_per_chunk, self.rays_per_chunk if i < self.nr_chunks - 1 else self.last_chunk)
-                for i in range(self.nr_chunks)]
-
-
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
-class Frame:
-    """A pinhole camera: K [3, 3], tf_world_cam [4, 4] (row-major [R|t], camera to world) and the image extents: what an image
-    reel holds per image."""
-
-    def __init__(self, K, tf_world_cam, height, width):
-        K, tf = torch.as_tensor(K), torch.as_tensor(tf_world_cam)
-        if tuple(K.shape) != (3, 3) or tuple(tf.shape) != (4, 4):
-            raise ValueError("Frame takes K [3, 3] and tf_world_cam [4, 4], got %s and %s" % (tuple(K.shape), tuple(tf.shape)))
-        if int(height) < 1 or int(width) < 1:
-            raise ValueError("empty frame: %d x %d" % (height, width))
-        self.K, self.tf_world_cam = _f32(K), _f32(tf)
-        self.height, self.width = int(height), int(width)
-
-    @staticmethod
-    def from_reel(reel, i):
-        """image `i` of anything with K_reel [I, 3, 3], tf_world_cam_reel [I, 4, 4] and rgb_reel [I, 3, H, W]"""
-        H, W = reel.rgb_reel.shape[-2:]
-        return Frame(reel.K_reel[i], reel.tf_world_cam_reel[i], H, W)
-
-    @property
-    def nr_pixels(self):
-        return self.height * self.width
-
-    def rot_cam_world(self):
-        """[3, 3]: the rotation of tf_cam_world = tf_world_cam^-1 (the transpose of a rigid transform's rotation)"""
-        return self.tf_world_cam[:3, :3].t().contiguous()
-
-
-def frame_rays(frame, first=0, count=None):
-    """-> (origins [n, 3], dirs [n, 3]) of the pixels [first, first + count) of `frame` (all of them from `first` on by
-    default); pixel p is (x, y) = (p % W, p / W) with its centre at +0.5"""
-    L.require_cuda(frame.K, frame.tf_world_cam)
-    first = int(first)
-    count = frame.nr_pixels - first if count is None else int(count)
-    if first < 0 or count < 0 or first + count > frame.nr_pixels:
-        raise ValueError("pixels [%d, %d) lie outside a %d x %d frame" % (first, first + count, frame.height, frame.width))
-    dev = frame.K.device
-    o = torch.empty((count, 3), dtype=torch.float32, device=dev)
-    d = torch.empty((count, 3), dtype=torch.float32, device=dev)
-    L.call("psdf_frame_rays", L.c_i(frame.height), L.c_i(frame.width), L.ptr(frame.K), L.ptr(frame.tf_world_cam), L.c_l(first),
-           L.c_i(count), L.ptr(o), L.ptr(d), L.stream())
-    return o, d
 
 
 def frame_composite_neus_raw(rs, sdf, gradients, rgb, inv_s, cos_anneal_ratio, height, width, pixel_first, rgb_img, normals_img,
@@ -275,41 +209,24 @@ class FrameRenderer:
         march, which bounds the rays of a chunk (FramePlan)."""
         t = self.trainer
         hp = t.hp
-        dev = self._check_devices(frame)
-        H, W = frame.height, frame.width
-        plan = FramePlan(H, W, hp.max_nr_samples_per_ray, pool_samples)
-        it = _IT_WINDOW_OPEN if it is None else it
+        dev = frame_device(frame, t.sdf)
+        plan = FramePlan(frame.height, frame.width, hp.max_nr_samples_per_ray, pool_samples)
+        it = IT_WINDOW_OPEN if it is None else it
         if isinstance(forced_variance, str):
             if forced_variance != "finish":
                 raise ValueError("forced_variance must be 'finish', a number or None, got %r" % (forced_variance,))
             forced_variance = hp.forced_variance_finish
         inv_s = self._inv_s(forced_variance)
         t._params_ready()                     # a data-parallel trainer's parameters may still be on their way
-
-        def planes(c):
-            return torch.empty((c, H, W), dtype=torch.float32, device=dev)      # every pixel belongs to one chunk, which writes it
-
+        planes = functools.partial(new_planes, frame, dev=dev)
         out = RenderedFrame(rgb=planes(3), rgb_bg=None if t.with_mask else planes(3), normals=planes(3),
                             normals_cam=planes(3) if camera_normals else None, weights_sum=planes(1))
         rot = frame.rot_cam_world() if camera_normals else None
         transmittance = torch.empty(plan.rays_per_chunk, dtype=torch.float32, device=dev)
-        grid_pool = t.grid.max_nr_samples
-        t.grid.max_nr_samples = int(pool_samples)        # the pool the plan was made for
-        try:
+        with sample_pool(t.grid, pool_samples):
             for first, count in plan.chunks():
                 self._chunk(frame, first, count, it, cos_anneal_ratio, inv_s, out, transmittance, rot)
-        finally:
-            t.grid.max_nr_samples = grid_pool
         return out
-
-    def _check_devices(self, frame):
-        """the kernels take raw pointers: no one else would notice a frame on another device than the models"""
-        L.require_cuda(frame.K, frame.tf_world_cam)
-        dev = frame.K.device
-        models_dev = self.trainer.sdf.encoding.lattice_values.device    # (a tensor's device carries its index; `t.dev` may be a bare "cuda")
-        if dev != models_dev or frame.tf_world_cam.device != dev:
-            raise L.PsdfError("the frame lives on %s, the models on %s" % (dev, models_dev))
-        return dev
 
     def _traced_chunk(self, frame, first, count, tracer, trace_args, it, out, rot, work):
         """one chunk of a sphere-traced frame, start to finish"""
@@ -342,17 +259,13 @@ class FrameRenderer:
         render_from_frame.py:335; `it` as in `render` (None: the lattice window fully open).  max_rays_per_chunk bounds the rays
         traced at once (FramePlan with one sample per ray)."""
         t = self.trainer
-        dev = self._check_devices(frame)
-        H, W = frame.height, frame.width
-        plan = FramePlan(H, W, 1, max_rays_per_chunk)
-        it = _IT_WINDOW_OPEN if it is None else it
-        t._params_ready()                     # a data-parallel trainer's parameters may still be on their way
         net = t.sdf
+        dev = frame_device(frame, net)
+        plan = FramePlan(frame.height, frame.width, 1, max_rays_per_chunk)
+        it = IT_WINDOW_OPEN if it is None else it
+        t._params_ready()                     # a data-parallel trainer's parameters may still be on their way
         tracer = SphereTracer(net.encoding, net.mlp_sdf, t.grid, t.sphere, _f32(net.window(it)))
-
-        def planes(c):
-            return torch.empty((c, H, W), dtype=torch.float32, device=dev)      # every pixel belongs to one chunk, which writes it
-
+        planes = functools.partial(new_planes, frame, dev=dev)
         out = TracedFrame(rgb=planes(3), normals=planes(3), normals_cam=planes(3) if camera_normals else None,
                           weights_sum=planes(1), depth=planes(1))
         rot = frame.rot_cam_world() if camera_normals else None
@@ -367,7 +280,6 @@ class FrameRenderer:
 
     def box(self):
         """the axis-aligned box of the scene, as a box_trace.Box: the cube of the occupancy grid"""
-        from .box_trace import Box
         g = self.trainer.grid
         return Box([g.m_grid_extent] * 3, g.m_grid_translation)
 
@@ -375,13 +287,11 @@ class FrameRenderer:
         """-> sdf_slice.SliceImage: the isolines of the SDF net on `plane` (a sdf_slice.SlicePlane), as
         render_from_frame.py:71-166 draws them; box: default `self.box()`; kw: sdf_slice.render_slice's (`it` None: the lattice
         window fully open)"""
-        from .sdf_slice import render_slice
         self.trainer._params_ready()
         return render_slice(self.trainer.sdf, plane, self.box() if box is None else box, size, **kw)
 
     def mesh_colorizer(self, it=None):
         """-> mesh_color.MeshColorizer over the SDF and the colour network (`it` None: the lattice window fully open)"""
-        from .mesh_color import MeshColorizer
         self.trainer._params_ready()
         return MeshColorizer(self.trainer.sdf, self.trainer.rgb, it)
 
@@ -398,10 +308,4 @@ class FrameRenderer:
         "volumetric": `render`, "traced": `render_traced`"""
         if mode not in ("volumetric", "traced"):
             raise ValueError("mode must be 'volumetric' or 'traced', got %r" % (mode,))
-        render = self.render if mode == "volumetric" else self.render_traced
-        frames = list(frames)
-        if not frames:
-            raise ValueError("render_views needs at least one frame")
-        if len({(f.height, f.width) for f in frames}) != 1:
-            raise ValueError("render_views takes frames of one size")
-        return torch.stack([render(f, **kwargs).rgb for f in frames])
+        return stack_views(self.render if mode == "volumetric" else self.render_traced, frames, **kwargs)

@@ -31,6 +31,7 @@ import torch
 
 from . import _lib as L
 from .bridge import OccupancyGrid
+from .frame import FramePlan, frame_device, frame_rays, new_planes, open_window
 from .net_eval import masked_sdf, one_row_head
 
 MAX_LINES = 32              # csrc/sdf_slice_plan.h
@@ -167,13 +168,12 @@ class _Field:
     """what both functions need of a net: the window, the 1-row head, the time on the device and the chunk buffers"""
 
     def __init__(self, net, it, time_val, n):
-        from .render import _IT_WINDOW_OPEN
         enc = self.enc = net.encoding
         self.P = P = int(enc.cfg.pos_dim)
         _check_time(P, time_val)
         L.require_cuda(enc.lattice_values)
         self.dev = dev = enc.lattice_values.device
-        self.window = net.window(_IT_WINDOW_OPEN if it is None else it).detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.window = open_window(net, it).detach().to(device=dev, dtype=torch.float32).contiguous()
         self.head = one_row_head(net.mlp_sdf, pack=True)      # channel 0 of the last layer is the SDF (models.py:190-192)
         self.time = torch.full((1,), float(time_val), dtype=torch.float32, device=dev) if P == 4 else None
         self.C, self.n = int(enc.cfg.channels), n
@@ -211,7 +211,7 @@ def slice_colorize_raw(style, size, first, count, sdf, skip, out):
 def render_slice(net, plane, box, size=500, style=IsoStyle(), it=None, time_val=None, max_points_per_chunk=_POOL):
     """-> SliceImage of the field of `net` (anything with `encoding`, `mlp_sdf` and `window(it)`) on `plane` inside `box` (a
     box_trace.Box), at `time_val` for a 4-D net.  size: cells per side (the reference: 500, 4000 for its full layer).  it: the
-    iteration whose coarse-to-fine window is used (None: fully open, the reference's 9999999).  Chunks of at most
+    iteration whose coarse-to-fine window is used (None: fully open, frame.IT_WINDOW_OPEN).  Chunks of at most
     max_points_per_chunk cells; per chunk four launches (points, masked encode, masked MLP, colorize) and no host wait; the
     buffers of the first chunk serve all of them."""
     S, chunk = int(size), int(max_points_per_chunk)
@@ -249,21 +249,17 @@ def cut_slice_into(net, plane, box, frame, rgb, depth, weights_sum, style=IsoSty
     """The layer as `frame` sees it, cut in place into rgb [3, H, W], depth [1, H, W] and weights_sum [1, H, W] of a view of the
     same frame: a pixel whose ray meets the layer inside the box, in front of the camera, with no surface (weights_sum == 0) or
     nearer than it (t < depth, the distance along the unit ray), takes the slice's colour, depth <- t and weights_sum <- 1; every
-    other pixel keeps its bits.  -> slice_mask [1, H, W].  Per chunk of at most max_rays_per_chunk rays (render.FramePlan with
+    other pixel keeps its bits.  -> slice_mask [1, H, W].  Per chunk of at most max_rays_per_chunk rays (frame.FramePlan with
     one sample per ray): rays -> begin -> `net_eval.masked_sdf` -> resolve.  No host wait."""
-    from .render import FramePlan, frame_rays
     _check_time(int(net.encoding.cfg.pos_dim), time_val)
-    L.require_cuda(frame.K, frame.tf_world_cam, net.encoding.lattice_values)
-    dev = net.encoding.lattice_values.device
-    if frame.K.device != dev or frame.tf_world_cam.device != dev:
-        raise L.PsdfError("the frame lives on %s, the net on %s" % (frame.K.device, dev))
+    dev = frame_device(frame, net)
     H, W = frame.height, frame.width
     rgb, depth, weights_sum = (_plane_of(frame, t, c, dev, n) for t, c, n in ((rgb, 3, "rgb"), (depth, 1, "depth"),
                                                                               (weights_sum, 1, "weights_sum")))
     fplan = FramePlan(H, W, 1, max_rays_per_chunk)
     f = _Field(net, it, time_val, fplan.rays_per_chunk)
     t_buf = torch.empty(f.n, dtype=torch.float32, device=dev)
-    mask = torch.empty((1, H, W), dtype=torch.float32, device=dev)      # every pixel belongs to one chunk, which writes it
+    mask = new_planes(frame, 1, dev)
     _, colours = _colour_args(style, dev)
     for first, count in fplan.chunks():
         o, d = frame_rays(frame, first, count)

@@ -64,6 +64,23 @@ int main() {
   }
   // a pool beyond int32
   CHECK(is(plan(1200, 1600, 64, (int64_t)1 << 40), 1920000, 1, 1920000));
+  // check_range: the elements [first, first + count) of a rows x cols image.  40 * 48 = 1920
+  CHECK(check_range(40, 48, 0, 1920) == PLAN_OK);                       // first = 0 and count = pixels
+  CHECK(check_range(40, 48, 77, 333) == PLAN_OK && check_range(7, 7, 0, 49) == PLAN_OK);
+  CHECK(check_range(40, 48, 1919, 1) == PLAN_OK);                       // the last element alone
+  CHECK(check_range(40, 48, 1919, 2) == PLAN_ERR_ARG);                  // the last element one past the end
+  CHECK(check_range(40, 48, 1, 1920) == PLAN_ERR_ARG && check_range(40, 48, 1920, 1) == PLAN_ERR_ARG);
+  CHECK(check_range(40, 48, 0, 1921) == PLAN_ERR_ARG);
+  CHECK(check_range(40, 48, 0, 0) == PLAN_ERR_ARG && check_range(40, 48, 5, -1) == PLAN_ERR_ARG);   // count = 0 is the caller's case
+  CHECK(check_range(40, 48, -1, 10) == PLAN_ERR_ARG);                   // a negative first
+  CHECK(check_range(0, 48, 0, 1) == PLAN_ERR_ARG && check_range(40, -3, 0, 1) == PLAN_ERR_ARG);
+  // 65 536 * 32 768 = 2^31 elements: unsupported whatever the range; one row less is a frame like any other
+  CHECK(check_range(65536, 32768, 0, 1) == PLAN_ERR_UNSUPPORTED && check_range(65536, 32768, -1, 1) == PLAN_ERR_UNSUPPORTED);
+  CHECK(check_range(65535, 32768, 2147450879, 1) == PLAN_OK && check_range(65535, 32768, 2147450880, 1) == PLAN_ERR_ARG);
+  // the order of the refusals: a bad extent or count before the size, the size before the position
+  CHECK(check_range(65536, 32768, 0, 0) == PLAN_ERR_ARG);
+  // first + count is never formed: a first near the top of int64 does not overflow
+  CHECK(check_range(40, 48, INT64_MAX, 1) == PLAN_ERR_ARG && check_range(40, 48, 0, INT64_MAX) == PLAN_ERR_ARG);
   if (failures) fprintf(stderr, "%d check(s) failed\n", failures);
   else printf("frame_plan_check: all checks passed\n");
   return failures;

@@ -46,6 +46,11 @@
 
 #include <hip/hip_runtime.h>
 static inline float rsqrtf(float x) { return 1.0f / sqrtf(x); }   // the device function of the ray kernel; the host's libm has none
+// cross-lane operations and launch geometry that csrc/composite_device.h (sdf_slice.hip takes it through frame_device.h) names in
+// helpers these kernels never call
+template <class T> T __shfl(T v, int, int) { return v; }
+template <class T> T __shfl_down(T v, int, int) { return v; }
+inline thread_local dim3 gridDim;
 
 #include "frame_rays.hip"
 #include "sdf_slice.hip"

@@ -35,9 +35,12 @@ def test_kernel_source_on_the_cpu_under_sanitizers(tmp_path):
 
 
 def test_the_kernel_file_stays_compilable_on_the_host():
-    src = open(os.path.join(CSRC, "box_trace.hip")).read()
-    assert not re.search(r"__shfl|__ballot|wave_sum|wave_incl|__builtin_amdgcn|__shared__|atomic", src)
-    assert '#include "composite_device.h"' in src and "normalize_eps" in src
+    src, shared = (open(os.path.join(CSRC, f)).read() for f in ("box_trace.hip", "frame_device.h"))
+    for text in (src, shared):
+        assert not re.search(r"__shfl|__ballot|wave_sum|wave_incl|__builtin_amdgcn|__shared__|atomic", text)
+    # the surface pixel, with its normalize_eps, is the shared header's
+    assert '#include "frame_device.h"' in src and "surface_hit(" in src and "st_surface(" in src and "box_inside(" in src
+    assert '#include "composite_device.h"' in shared and "normalize_eps" in shared
 
 
 @pytest.fixture(scope="module")

@@ -57,12 +57,16 @@ def _code(name):
 
 
 def test_the_kernels_keep_to_their_files_and_share_what_exists():
-    # the resolve kernel's file stays compilable against hip_on_host: no cross-lane operation, no LDS; it calls normalize_eps
-    resolve = _code("frame_trace.hip")
-    assert not re.search(r"__shfl|__ballot|wave_sum|wave_incl|__builtin_amdgcn|__shared__|__syncthreads|atomic", resolve)
-    assert '#include "composite_device.h"' in resolve and len(re.findall(r"\bnormalize_eps\s*\(", resolve)) == 2
-    assert "sqrtf" not in resolve and "fmaxf" not in resolve
-    assert "(q.x * d.x + q.y * d.y) + q.z * d.z" in resolve
+    # the resolve kernel's file and the header of the surface pixel stay compilable against hip_on_host: no cross-lane operation,
+    # no LDS; the pixel is frame_device.h's, which calls normalize_eps for the normal and for the camera normal
+    resolve, shared = _code("frame_trace.hip"), _code("frame_device.h")
+    for code in (resolve, shared):
+        assert not re.search(r"__shfl|__ballot|wave_sum|wave_incl|__builtin_amdgcn|__shared__|__syncthreads|atomic", code)
+        assert "sqrtf" not in code and "fmaxf" not in code
+    assert '#include "composite_device.h"' in shared and len(re.findall(r"\bnormalize_eps\s*\(", shared)) == 2
+    assert "(q.x * d.x + q.y * d.y) + q.z * d.z" in shared
+    assert '#include "frame_device.h"' in resolve and "normalize_eps" not in resolve
+    assert len(re.findall(r"\bsurface_hit\s*\(", resolve)) == 1 and len(re.findall(r"\bst_surface\s*\(", resolve)) == 1
     # the select kernels live next to check_occupancy_kernel and use the one Grid: its lookup is defined once in the tree
     sampling = _code("sampling.hip")
     for f in os.listdir(CSRC):
