@@ -1480,6 +1480,7 @@ int psdf_mlp_backward_data_masked(int n_layers, const int* dims, int64_t N, cons
   hipStream_t st = (hipStream_t)stream;
   const int ti0 = p.tiles[0], t1 = p.tiles[1], t2 = p.tiles[2], t3 = (n_layers == 4) ? p.tiles[3] : 0,
             to = p.tiles[n_layers];
+  psdf::g_last_path[psdf::PATH_MLP_BWD] = 1;   // the fp32-MFMA kernel or nothing: psdf_last_path(1) speaks of THIS call
 #define CASE(I, A, B, C, O, D, DW, DX, MASKED, DBL, PLUS)                                        \
   PSDF_IF(MASKED, if (ti0 == I && t1 == A && t2 == B && t3 == C && to == O && p.final_dot == D) \
     return launch_bwd<I, A, B, C, O, D>(p, N, X, dY, dX, a, st);)

@@ -10,6 +10,9 @@ Below the baseline net: the float64 evaluator of the DOUBLE backward (f64_double
 its input families and its case lists, for tests/test_mlp_double_backward_float64.py and
 tests/test_gpu_mlp_double_backward_float64.py.
 
+Last: the nets, batch sizes, launch arithmetic and skip patterns of the single-wave fp32-MFMA kernels in every launch form (SW_*),
+for tests/test_mlp_single_wave_cases.py (host) and tests/test_gpu_mlp_single_wave_float64.py.
+
 No test in here; everything is generated on the CPU from seeded generators, so the host tests and the GPU tests see the same
 numbers."""
 import torch
@@ -376,3 +379,224 @@ DBL_NUMERICS_CASES = [DblCase(d, N_DBL, lattice, v, misses, plus=d is DBL_REF, t
 # 1: a single sample; 17: one tile + 1; 63 / 64 / 65: one workgroup's four tiles -1 / exact / +1; 16 423: see N_DBL; 32 807: three
 # waves take a third tile, so the two-slot prefetch returns to its first slot
 DBL_GEOMETRY_CASES = [DblCase(d, N, plus=d is DBL_REF) for d in (DBL_BASE, DBL_REF) for N in (1, 17, 63, 64, 65, N_DBL, 32_807)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the SINGLE-WAVE fp32-MFMA kernels (mlp_bwd_kernel of csrc/mlp_bwd.hip through psdf_mlp_backward and
+# psdf_mlp_backward_data_masked, mlp_fwd_kernel of csrc/mlp.hip through psdf_mlp_forward): every row of PSDF_MLP16_ROWS
+# (csrc/mlp_dispatch.h) in every launch form it has, shared by tests/test_mlp_single_wave_cases.py (host) and
+# tests/test_gpu_mlp_single_wave_float64.py
+
+# launch forms of mlp_bwd_kernel: "dwdx" psdf_mlp_backward(dX, dW); "dw" (NULL, dW); "dx" (dX, NULL): no accumulators, up to 512
+# workgroups; "masked" psdf_mlp_backward_data_masked: the "dx" launch with a sample mask
+SW_FORMS = ("dwdx", "dw", "dx", "masked")
+_ALL, _NO_MASK, _DX = SW_FORMS, ("dwdx", "dw", "dx"), ("dx",)
+# (dims, forms): one or more nets per row of PSDF_MLP16_ROWS, in every form the row has.  (The one-output nets of the 64-wide rows
+# have their dW+dX form in tests/test_gpu_mlp_baseline_numerics.py as well; here it is what their other forms are compared with.)
+# The colour head's dW+dX form reaches this kernel only with PSDF_MLP_WIDE_SPLIT=f32
+SW_NETS = [
+    ((36, 64, 64, 64, 1), _ALL), ((35, 64, 64, 64, 3), _ALL), ((44, 64, 64, 64, 4), _ALL),                  # (3, 4, 4, 4, 1)
+    ((52, 64, 64, 64, 1), _ALL), ((61, 64, 64, 64, 2), _ALL),                                               # (4, 4, 4, 4, 1)
+    ((20, 64, 64, 64, 1), _ALL), ((27, 64, 64, 64, 1), _ALL),                                               # (2, 4, 4, 4, 1)
+    ((52, 32, 32, 32, 1), _ALL), ((36, 32, 32, 32, 1), _ALL), ((20, 32, 32, 32, 1), _ALL),                  # (4|3|2, 2, 2, 2, 1)
+    ((51, 30, 32, 28, 2), _ALL),
+    ((52, 32, 32, 32, 33), _NO_MASK), ((36, 32, 32, 32, 33), _NO_MASK), ((51, 30, 32, 28, 40), _NO_MASK),   # (4|3, 2, 2, 2, 3)
+    ((52, 64, 64, 64, 65), _DX), ((52, 64, 64, 64, 33), _DX), ((36, 64, 64, 64, 33), _DX),    # (4, 4, 4, 4, 5|3), (3, 4, 4, 4, 3)
+    ((50, 60, 64, 56, 70), _DX),
+    ((80, 64, 64, 3), _NO_MASK),                                                                            # (5, 4, 4, 0, 1)
+]
+SW_REF, SW_BASE, SW_HEAD = (52, 32, 32, 32, 33), (36, 64, 64, 64, 1), (80, 64, 64, 3)
+# batches, the smallest at which each launch rule of launch_bwd_nw / launch_bwd changes (sw_launch below restates them;
+# tests/test_mlp_single_wave_cases.py asserts every claim made here).  The dW forms run min(ceil(tiles / W), 256) workgroups of
+# W = 4 waves (8 for 32-wide nets from 2^17 samples on), the data-gradient forms min(ceil(tiles / 4), 512) of 4 waves; wave w of
+# workgroup b walks the 16-sample tiles 4 b + w, + 4 x workgroups, ..
+#   1: one sample; 17: one tile + 1; 63 / 64 / 65: one workgroup's four tiles - 1 / exact / + 1 (65: a second workgroup with one
+#   wave at work on a tile of one sample)
+#   16 423 = 256 x 4 x 16 + 39: dW forms: every wave one tile, three waves a second one (two whole tiles and the partial last
+#   tile of 7 samples); data-gradient forms: 1027 tiles on 257 workgroups, no wave a second tile
+#   32 807 = 512 x 4 x 16 + 39: the same point for the data-gradient forms; dW forms: every wave two tiles, three a third
+SW_N_FULL = (1, 17, 63, 64, 65, 16_423, 32_807)
+SW_N_DW, SW_N_DX = 16_423, 32_807
+# the eight-wave threshold of launch_bwd (32-wide nets, dW forms): 2^17 - 1: four waves, eight tiles each; 2^17 + 19: eight waves,
+# four tiles each and two a fifth.  (Baseline-shaped nets, 64 x 3 -> 1, leave this kernel at 2^18 with parameter gradients.)
+SW_N_EIGHT = ((1 << 17) - 1, (1 << 17) + 19)
+SW_EIGHT_NETS = (SW_REF, (36, 32, 32, 32, 1))
+# the fp32 forward (mlp_fwd_kernel): min(ceil(tiles / 4), 1024) workgroups of 4 waves on 32-sample tiles.  131 111 = 1024 x 4 x
+# 32 + 39: past the cap, two waves take a second tile, the last tile has 7 samples
+SW_N_FWD = (65, 131_111)
+# row (4, 4, 2, 1) of PSDF_MLP32_ROWS below the colour net's own widths 111-128-128-64-3, every width short of its last tile
+# (a first hidden layer of 96 would be three 32-wide tiles: no row, no forward kernel)
+SW_COLOUR_TILES = (100, 112, 128, 48, 2)
+SW_FWD_NETS = [d for d, _ in SW_NETS] + [SW_COLOUR_TILES]
+# rows of PSDF_MLP32_ROWS (32-wide tiles t1, t2, t3, to, outputs <= 4) with the SPLIT column: psdf_mlp_forward runs the split-bf16
+# kernel (path 2) where the net's split image fits 80 KB, the fp32-MFMA kernel (path 1) on the other rows
+SW_FWD_SPLIT_ROWS = {(2, 2, 2, 1, True), (1, 1, 1, 1, True), (1, 1, 1, 2, False), (2, 2, 0, 1, True)}
+SW_FWD_F32_ROWS = {(2, 2, 2, 3, False), (2, 2, 2, 2, False), (4, 4, 2, 1, True)}
+
+
+class SwCase:
+    """one case of the single-wave kernels: dims (3 or 4 layers), N, the launch forms it runs in, tails (W_1, b_1 times
+    TAILS_SCALE)"""
+
+    def __init__(self, dims, N, forms, tails=False):
+        self.dims, self.N, self.forms, self.tails = tuple(dims), N, tuple(forms), tails
+
+    def key(self):
+        return (self.dims, self.N, self.tails)
+
+    def __repr__(self):
+        return "%s N=%d%s" % ("-".join(map(str, self.dims)), self.N, " tails" if self.tails else "")
+
+
+def _sw_cases():
+    cases = []
+    for dims, forms in SW_NETS:
+        dx_row = forms == _DX
+        Ns = SW_N_FULL if dims in (SW_REF, SW_BASE) else (65, SW_N_DX if dx_row else SW_N_DW)
+        cases += [SwCase(dims, N, forms) for N in Ns]
+    # the masked walk of a SECOND tile: at 16 423 samples the data-gradient launch gives every wave one tile only, so one
+    # net per masked row (36-64-64-64-1 has it in its full list) also runs masked at 32 807
+    cases += [SwCase(d, SW_N_DX, ("masked",)) for d in ((52, 64, 64, 64, 1), (20, 64, 64, 64, 1), (52, 32, 32, 32, 1),
+                                                        (36, 32, 32, 32, 1), (20, 32, 32, 32, 1))]
+    cases += [SwCase(d, N, ("dwdx", "dw")) for d in SW_EIGHT_NETS for N in SW_N_EIGHT]
+    return cases
+
+
+SW_CASES = _sw_cases()
+SW_TAILS_CASE = SwCase(SW_REF, SW_N_DW, _NO_MASK, tails=True)
+
+
+def mlp_net(dims, seed):
+    """the torch.nn.Linear of any depth with biases ~ N(0, 0.1) (sdf_net for other depths)"""
+    torch.manual_seed(seed)
+    lin = [torch.nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1)]
+    for l in lin:
+        torch.nn.init.normal_(l.bias, 0.0, 0.1)
+    return lin
+
+
+def head_inputs(N, gen):
+    """[N, 80] fp32, what the background colour head reads: 64 feature columns ~ randn, 16 columns in [-1, 1]"""
+    return torch.cat([torch.randn(N, 64, generator=gen), torch.rand(N, 16, generator=gen) * 2 - 1], 1)
+
+
+def sw_case(dims, N, tails=False):
+    """-> (lin, x [N, K0], gy [N, out]) seeded by the case itself.  x: the encoding's layout at lattice 1e-2 where
+    sdf_layout(K0), the head's inputs for 80 columns, plain_inputs otherwise; gy: randn with one row in 16 exactly 0 (rows
+    5, 21, ..: the dX rows of these samples have S == 0)"""
+    import zlib
+    dims = tuple(dims)
+    seed = zlib.crc32(repr((dims, N, tails)).encode())
+    gen = torch.Generator().manual_seed(seed)
+    lin = mlp_net(dims, seed)
+    if tails:
+        with torch.no_grad():
+            lin[0].weight.mul_(TAILS_SCALE)
+            lin[0].bias.mul_(TAILS_SCALE)
+    K0 = dims[0]
+    x = sdf_inputs(K0, N, 1e-2, 0, gen) if sdf_layout(K0) else head_inputs(N, gen) if K0 == 80 else plain_inputs(K0, N, gen)
+    gy = torch.randn(N, dims[-1], generator=gen)
+    gy[5::16] = 0.0
+    return lin, x, gy
+
+
+def sw_sig16(dims):
+    """tile signature of PSDF_MLP16_ROWS (_sig16 of tests/test_dispatch_tables.py)"""
+    t = [(w + 15) // 16 for w in dims]
+    return (t[0], t[1], t[2], t[3] if len(dims) == 5 else 0, t[-1], dims[-1] <= 4)
+
+
+def sw_sig32(dims):
+    t = [(w + 31) // 32 for w in dims]
+    return (t[1], t[2], t[3] if len(dims) == 5 else 0, t[-1], dims[-1] <= 4)
+
+
+def _walk(ntiles, workgroups, waves):
+    """wave w of workgroup b walks the tiles waves b + w, + waves x workgroups, ..: the launch in numbers"""
+    stride = workgroups * waves
+    return {"waves": waves, "workgroups": workgroups, "tiles": ntiles, "stride": stride,
+            "least": ntiles // stride,                              # tiles every wave of the launch walks
+            "most": -(-ntiles // stride),                           # tiles of the busiest wave
+            "extra": ntiles % stride}                               # waves that walk `most` tiles where most > least
+
+
+def sw_launch(dims, N, form):
+    """launch_bwd and launch_bwd_nw of csrc/mlp_bwd.hip restated: workgroups, waves per workgroup, tiles per wave, and whether
+    the last 16-sample tile is partial (`last`: its samples)"""
+    assert form in SW_FORMS
+    ntiles = -(-N // 16)
+    with_dw = form in ("dwdx", "dw")
+    narrow = all(w <= 32 for w in dims[1:-1])
+    waves = 8 if (with_dw and narrow and N >= 1 << 17) else 4      # the data-gradient kernel is built for four waves only
+    r = _walk(ntiles, min(-(-ntiles // waves), 256 if with_dw else 512), waves)
+    r["last"] = N - 16 * (ntiles - 1)
+    return r
+
+
+def fwd_launch(N):
+    """launch_fwd of csrc/mlp.hip (the fp32 forward) restated, 32-sample tiles"""
+    ntiles = -(-N // 32)
+    r = _walk(ntiles, min(-(-ntiles // 4), 1024), 4)
+    r["last"] = N - 32 * (ntiles - 1)
+    return r
+
+
+def fwd_split_image_bytes(dims):
+    """bytes of the split-bf16 image of psdf_mlp_pack (make_split_plan of csrc/mlp_device.h): 16-byte records"""
+    nl = len(dims) - 1
+    t = [(w + 31) // 32 for w in dims]
+    dot = dims[-1] <= 4
+    rec = f = 0
+    for l in range(nl):
+        last_dot = l == nl - 1 and dot
+        if not last_dot:
+            rec += t[l + 1] * ((dims[0] + 15) // 16 if l == 0 else 2 * t[l]) * 3 * 64
+        f += (dims[-1] * t[l] * 32 + 4) if last_dot else t[l + 1] * 32
+    return (rec + (f + 3) // 4) * 16
+
+
+def fwd_path(dims):
+    """what psdf_last_path(2) must say after psdf_mlp_forward of this net, by the table"""
+    sig = sw_sig32(dims)
+    if sig in SW_FWD_SPLIT_ROWS and fwd_split_image_bytes(dims) <= 80 * 1024:
+        return 2
+    assert sig in SW_FWD_SPLIT_ROWS | SW_FWD_F32_ROWS, dims
+    return 1
+
+
+# skip patterns of the masked form (16-sample tiles; a tile is skipped when ALL its samples are masked)
+SW_MASKS = ("none", "all", "interior_tile", "fifteen_of_sixteen", "last_tile", "every_second_tile")
+# where a wave walks two tiles (N = 32 807): its first tile masked and its second live, and the reverse
+SW_MASKS_TWO_TILES = ("every_second_tile", "first_round", "second_round")
+
+
+def sw_mask(N, pattern, stride=2048):
+    """-> (skip [N] uint8, skipped [N] bool: the samples of fully masked tiles, whose dX columns must keep their contents).
+    interior_tile: tile tiles // 2; fifteen_of_sixteen: tile 1 but for its sample 7 (a live tile: all 16 are evaluated);
+    last_tile: the partial last tile; every_second_tile: the odd tiles; first_round / second_round: the tiles below / from
+    `stride` on (the data-gradient launch's waves x workgroups)"""
+    ntiles = -(-N // 16)
+    tile = torch.arange(N) // 16
+    if pattern == "none":
+        skip = torch.zeros(N, dtype=torch.bool)
+    elif pattern == "all":
+        skip = torch.ones(N, dtype=torch.bool)
+    elif pattern == "interior_tile":
+        assert 0 < ntiles // 2 < ntiles - 1
+        skip = tile == ntiles // 2
+    elif pattern == "fifteen_of_sixteen":
+        assert ntiles > 2
+        skip = tile == 1
+        skip[16 + 7] = False
+    elif pattern == "last_tile":
+        skip = tile == ntiles - 1
+    elif pattern == "every_second_tile":
+        skip = tile % 2 == 1
+    elif pattern == "first_round":
+        skip = tile < stride
+    else:
+        assert pattern == "second_round", pattern
+        skip = tile >= stride
+    live_tiles = torch.zeros(ntiles, dtype=torch.bool)
+    live_tiles[tile[~skip]] = True
+    return skip.to(torch.uint8), ~live_tiles[tile]

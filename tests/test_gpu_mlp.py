@@ -1,6 +1,10 @@
 """GPU parity: fused MFMA MLP vs the unmodified torch.nn fp32 evaluator (the reference's own MLP code path,
 permuto_sdf_py/models/models.py:153-161).  Tolerance 2e-5 relative to the output scale (fp32, different
-summation order; GELU via a <1-ulp erf)."""
+summation order; GELU via a <1-ulp erf).
+
+These are max-norm checks on randn inputs at small batches.  Every entry of every tensor of the single-wave fp32-MFMA kernels,
+in every launch form and past the batch sizes at which a wave walks a second tile, is held to float64 in
+tests/test_gpu_mlp_single_wave_float64.py."""
 import pytest
 import torch
 
